@@ -16,9 +16,12 @@ scaling).
 Rank 0 prints ONE compact JSON line of at most LINE_CAP bytes (the driver
 keeps the last ~8 KB of stdout): the contract's fields, the dominant kernel's
 roofline, the CPU baseline and each object's rate; --detail PATH writes the
-full record.  Objects run in order -- headline, cfg2, cfg5, f4, then the
-validator-sharded ones -- each secondary one guarded and under a deadline
-(Phases), so a failure or a stuck collective costs only that object.
+full record.  A plain run times the headline only (with the roofline its own
+stage events give); --full adds the other objects, in order -- the headline's
+leaf-reuse variant, cfg2, cfg5, f4, then the validator-sharded ones and the CPU
+baselines -- each secondary one guarded and under a deadline (Phases), so a
+failure or a stuck collective costs only that object.  --dump-outputs DIR
+writes what the headline's last timed step computed (dump_outputs).
 
 Validator-sharded simulation (the `validators` object of the same line, or
 the headline with --mode validators): the N validators are split over the
@@ -76,6 +79,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: its leaf-reuse variant and cfg2's encode+Merkle "
+                         "rate, the cfg2 / cfg5 objects, the f4 leg, the validator-sharded objects "
+                         "and the CPU baselines (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the headline's last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB: fixed seeded samples of the large "
+                         "buffers); the inputs depend on the arguments only")
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
     ap.add_argument("--count", type=int, default=0, help="instances per GPU (default: config)")
     ap.add_argument("--vcount", type=int, default=0,
@@ -214,6 +225,51 @@ def gen_present(torch, seed, first, count, n, n_erase, dev):
         hit = (cum == r.view(-1, 1)) & (pres == 1)
         pres[hit] = 0
     return pres
+
+
+# ------------------------------------------------------------ --dump-outputs --
+DUMP_CAP = 64 << 20    # bytes of all the .npy files of one rank
+
+
+def _dump_sample(torch, np, t, budget, rng):
+    """`t` as a float32 array: whole if it has at most `budget` elements, else
+    a fixed sample of it as [rows][row bytes] -- seeded, sorted rows of
+    dimension 0 and, where one row alone is too large, columns of the row."""
+    t2 = t.reshape(t.shape[0], -1) if t.dim() > 1 else t.reshape(-1, 1)
+    rows, cols = t2.shape
+    if rows * cols > budget:
+        nr = min(rows, max(1, budget // cols) if cols <= budget else 64)
+        ri = np.sort(rng.choice(rows, nr, replace=False))
+        t2 = t2.index_select(0, torch.from_numpy(ri).to(t.device))
+        if nr * cols > budget:
+            ci = np.sort(rng.choice(cols, budget // nr, replace=False))
+            t2 = t2.index_select(1, torch.from_numpy(ci).to(t.device))
+        t = t2
+    return t.to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(torch, path, rank, tensors, sums=()):
+    """--dump-outputs: every (name, tensor, element budget) of `tensors` as
+    path/<name>.npy in float32 (_dump_sample; the sample's indices depend on
+    SEED and the shapes only), and every (name, [rows][cols] uint8 tensor) of
+    `sums` as the float64 byte sum of each row (exact: all of a large buffer
+    in one number per instance).  Rank r > 0 writes <name>_rank<r>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(SEED)
+    sfx = "" if rank == 0 else "_rank%d" % rank
+    total = 0
+    for name, t, budget in tensors:
+        a = _dump_sample(torch, np, t, budget, rng)
+        total += a.nbytes
+        np.save(os.path.join(path, name + sfx + ".npy"), a)
+    for name, t in sums:
+        chunk = max(1, (1 << 28) // max(1, t.shape[1]))
+        a = torch.cat([t[lo:lo + chunk].sum(dim=1, dtype=torch.float64)
+                       for lo in range(0, t.shape[0], chunk)]).cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(path, name + sfx + ".npy"), a)
+    assert total <= DUMP_CAP, total
 
 
 # --------------------------------------------------------------- accounting --
@@ -646,6 +702,20 @@ def run_instances(args, n, plen, count, erase, rank, world, dev, local, config=N
         # the outputs of each pipe's last timed step, from garbage rows
         check("last timed step", sorted({(warm + j) % npipe for j in range(args.steps)}))
         verified = True
+    if args.dump_outputs and config == args.config:
+        # what a caller of the step receives, from the pipe of the last timed
+        # step: the shards (erased rows rebuilt by the decode), the proposer's
+        # tree, the proofs, the validation flags, the agreed roots, and the
+        # decode's tree, payloads, lengths and status
+        B = bufs[(warm + args.steps - 1) % npipe]
+        M = 1 << 20
+        dump_outputs(torch, args.dump_outputs, rank,
+                     [("payload_out", B["out"][:, :plen], 4 * M), ("shards", B["slab"], 3 * M),
+                      ("tree_nodes", B["nodes"], M), ("decode_tree_nodes", B["nodes2"], M),
+                      ("proof_digests", B["digests"], M), ("proof_lengths", B["ndig"], M // 4),
+                      ("proof_ok", B["ok"], M), ("roots", B["roots"], M),
+                      ("payload_len", B["plen_out"], M // 4), ("status", B["status"], M // 4)],
+                     sums=[("payload_out_row_sums", B["out"][:, :plen])])
     stages = {}
     for sb in all_rb:
         for st_name, (ms, cnt) in sb.profile_read().items():
@@ -970,6 +1040,16 @@ def run_validators(args, n, plen, count, rank, world, dev, local, config=None):
     else:
         xms = timer.elapsed_ms() / args.steps if world > 1 else 0.0
     timer.timing = False
+    if args.dump_outputs and args.mode == "validators" and config is None:
+        # validator headline: what the object of the last timed step decoded
+        # (the first sub-batch's on the serial multi-rank schedule)
+        last = pipe_sbs[(args.steps - 1) % npipe] if npipe > 1 else sb
+        M = 1 << 20
+        dump_outputs(torch, args.dump_outputs, rank,
+                     [("payload_out", last.out[:, :plen], 4 * M), ("value_proof_ok", last.ok_v, M),
+                      ("decided", last.decided, M), ("payload_len", last.plen_out, M // 4),
+                      ("status", last.status, M // 4)],
+                     sums=[("payload_out_row_sums", last.out[:, :plen])])
     # per-rank record of the exchange: world, backend, and per collective the
     # calls and bytes this rank sent during the timed steps (rank 0 prints all)
     mine = {"rank": rank, "world": world, "backend": ex.backend,
@@ -1584,7 +1664,8 @@ def real_phases(args, world, rank, dev, local):
     n, plen, count, erase, vcount = CONFIGS[args.config]
     count = args.count or count
     vcount = args.vcount or vcount
-    both = args.mode == "both" and args.config == "cfg3"
+    # a plain run times the headline alone; --full adds every other object
+    both = args.full and args.mode == "both" and args.config == "cfg3"
     ph = []
 
     def fresh(fn):
@@ -1594,7 +1675,8 @@ def real_phases(args, world, rank, dev, local):
         return run
     if args.mode in ("instances", "both"):
         ph.append(("head", lambda: run_instances(args, n, plen, count, erase, rank, world, dev,
-                                                 local, encode_merkle=args.config == "cfg2")))
+                                                 local, leaf_reuse=args.full,
+                                                 encode_merkle=args.full and args.config == "cfg2")))
     if both and not args.no_riders:
         # BASELINE's other GPU configs, instance-sharded over the ranks like the
         # headline: cfg2 (N=16, 1 MiB x 4096, with its own encode+Merkle
@@ -1606,9 +1688,9 @@ def real_phases(args, world, rank, dev, local):
                                                 rank, world, dev, local, config=cfg, streams=1,
                                                 leaf_reuse=False, encode_merkle=cfg == "cfg2",
                                                 pipes=args.rider_pipes if cfg == "cfg2" else 1))))
-    if args.f4_checks > 0:
+    if args.full and args.f4_checks > 0:
         ph.append(("threshold_decrypt", fresh(lambda: run_threshold(args, rank, world, dev))))
-    if args.mode in ("validators", "both"):
+    if args.mode == "validators" or (args.full and args.mode == "both"):
         ph.append(("validators", fresh(lambda: run_validators(args, n, plen, vcount, rank, world,
                                                               dev, local))))
     if both and not args.no_cfg4:
@@ -1665,9 +1747,9 @@ def run_bench(args, world, rank, dev, local, phases, backend_cpu=False, cpu_fn=N
 
 
 def take_cpu_baselines(args, rank, world, res, n, plen, erase):
-    """Rank 0 of a one-rank run: the pipeline's CPU baseline, and the f4
-    leg's (added to its object)."""
-    if rank != 0 or world != 1 or args.no_cpu:
+    """Rank 0 of a one-rank --full run: the pipeline's CPU baseline, and the
+    f4 leg's (added to its object)."""
+    if rank != 0 or world != 1 or args.no_cpu or not args.full:
         return None
     f4 = res.get("threshold_decrypt")
     if f4 is not None and "error" not in f4:

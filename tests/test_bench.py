@@ -56,7 +56,7 @@ def test_f4_leg_host_helpers():
 
 @pytest.mark.gpu
 def test_bench_line_small(tmp_path):
-    """The whole default line at small sizes on the GPU, as the driver runs it
+    """The whole --full line at small sizes on the GPU, as the driver runs it
     (one process, N=1): instance mode with its leaf-reuse variant, the cfg2 /
     cfg5 objects, the f4 leg, then both validator objects on the one-rank
     schedule (state machine beside the next step, two step pipelines).
@@ -64,7 +64,7 @@ def test_bench_line_small(tmp_path):
     fit the driver's tail (LINE_CAP) and carry every object, none of them an
     error, and --detail the full record."""
     detail = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--count", "512",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--count", "512",
                         "--vcount", "256", "--rider-count", "64", "--steps", "2", "--warmup", "2",
                         "--no-cpu", "--detail", detail,
                         "--f4-checks", "4096", "--f4-steps", "1"],
@@ -94,6 +94,72 @@ def test_bench_line_small(tmp_path):
     assert "state_machine_overlapped" in full["validators"]["stages_ms_per_step"]
     assert full["validators"]["config"]["step_pipelines"] == 2
     assert "stages" in full["roofline"] and "encode_merkle" in full["cfg2"]
+
+
+def test_dump_outputs_samples_are_fixed(tmp_path):
+    """--dump-outputs on the host: a small buffer is written whole, a large
+    one as a sample whose indices depend on the seed and the shapes only
+    (rows of dimension 0, then columns where one row exceeds the budget), the
+    row sums cover every byte, everything is float32 / float64."""
+    g = torch.Generator().manual_seed(3)
+    small = torch.randint(0, 256, (5, 3, 7), dtype=torch.uint8, generator=g)
+    big = torch.randint(0, 256, (40, 1000), dtype=torch.uint8, generator=g)
+    wide = torch.randint(0, 256, (70, 5000), dtype=torch.uint8, generator=g)
+    flat = torch.arange(9, dtype=torch.int32)
+    got = []
+    for d in ("a", "b"):
+        p = str(tmp_path / d)
+        bench.dump_outputs(torch, p, 0, [("small", small, 1000), ("big", big, 8000),
+                                         ("wide", wide, 640), ("flat", flat, 100)],
+                           sums=[("sums", big[:, :999])])
+        got.append({f[:-4]: np.load(os.path.join(p, f)) for f in sorted(os.listdir(p))})
+    a, b = got
+    assert sorted(a) == ["big", "flat", "small", "sums", "wide"]
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(a[k].dtype == np.float32 for k in ("small", "big", "wide", "flat"))
+    assert a["small"].shape == (5, 3, 7) and np.array_equal(a["small"], small.numpy())
+    assert np.array_equal(a["flat"], np.arange(9))
+    assert a["big"].shape == (8, 1000) and a["wide"].shape == (64, 10)
+    bn, wn = big.numpy(), wide.numpy()
+    rows = [i for i in range(40) if any(np.array_equal(bn[i], r) for r in a["big"])]
+    assert len(rows) == 8 and np.array_equal(bn[rows], a["big"])     # sorted rows of `big`
+    assert all(any(set(r) <= set(wn[i]) for i in range(70)) for r in a["wide"])
+    assert a["sums"].dtype == np.float64
+    assert np.array_equal(a["sums"], bn[:, :999].sum(axis=1, dtype=np.int64))
+    bench.dump_outputs(torch, str(tmp_path / "r1"), 1, [("flat", flat, 100)])
+    assert os.listdir(str(tmp_path / "r1")) == ["flat_rank1.npy"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dump(tmp_path):
+    """A plain run at a small size: the headline alone (none of the --full
+    objects, no CPU baseline), --steps timed steps, and --dump-outputs with
+    the last timed step's outputs: every decode Ok, every proof valid, the
+    payload lengths, and the byte sum of every decoded payload equal to the
+    generated payload's."""
+    out = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--count",
+                        "96", "--steps", "3", "--warmup", "1", "--dump-outputs", out],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _line(r.stdout)
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 3
+    assert line["metric"] == bench.METRIC and line["unit"] == "GB/s" and line["dtype"] == "u8"
+    assert line["higher_is_better"] is True and line["cpu_baseline"] is None
+    assert line["roofline"]["frac"] > 0
+    for key in ("leaf_reuse", "cfg2", "cfg5", "threshold_decrypt", "validators",
+                "validators_cfg4"):
+        assert key not in line, key
+    n, plen = bench.CONFIGS["cfg3"][:2]
+    d = {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+    assert sum(a.nbytes for a in d.values()) <= bench.DUMP_CAP
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert d["status"].shape == (96,) and not d["status"].any()
+    assert (d["payload_len"] == plen).all() and (d["proof_ok"] == 1).all()
+    assert d["proof_ok"].shape == (96, n) and d["roots"].shape == (96, 32)
+    assert np.array_equal(d["tree_nodes"], d["decode_tree_nodes"])
+    pay = bench.gen_payloads(torch, bench.SEED, 0, 96, plen, plen, "cpu").numpy()
+    assert np.array_equal(d["payload_out_row_sums"], pay.sum(axis=1, dtype=np.int64))
 
 
 # ------------------------------------------------ the line and its phases --
