@@ -170,3 +170,23 @@ pub fn pairing_eq(a: &[u8; 96], b: &[u8; 192], c: &[u8; 96], d: &[u8; 192]) -> b
     }
     r == 1
 }
+
+/// `PublicKeySet::decrypt` up to the group element g (threshold_decrypt.rs:
+/// 232-252): the Lagrange interpolation at 0 of `shares` in G1 on the GPU,
+/// share i coming from node `indices[i]`.  Returns g in the pairing crate's
+/// uncompressed and compressed encodings (the caller's `xor_with_hash` hashes
+/// the compressed one), or `None` for an invalid share or a repeated index
+/// (the crate's `DuplicateEntry`).
+pub fn decrypt_combine(shares: &[[u8; 96]], indices: &[u32]) -> Option<([u8; 96], [u8; 48])> {
+    assert_eq!(shares.len(), indices.len());
+    let (mut g96, mut g48) = ([0u8; 96], [0u8; 48]);
+    let st = unsafe {
+        ffi::hbrbc_decrypt_combine(shares.as_ptr() as *const u8, indices.as_ptr(), shares.len(),
+                                   g96.as_mut_ptr(), g48.as_mut_ptr())
+    };
+    match st {
+        0 => Some((g96, g48)),
+        100 => None, // HBRBC_E_INVALID_ARG: the group's status was 2 or 3
+        _ => fail_loudly(st), // a device error panics
+    }
+}

@@ -148,6 +148,13 @@ def lib():
                                                             _P, _P]),
         "hbrbc_pairing_check": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                                ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]),
+        "hbrbc_g1_combine_workspace_size": (_S, [_S, _S]),
+        "hbrbc_lagrange_coeffs": (ctypes.c_int, [_P, _P, _S, _P, _P, _P]),
+        "hbrbc_g1_lincomb_prepared": (ctypes.c_int, [_P, _S, _P, _P, _P, _S, _P, _P, _P, _P, _P]),
+        "hbrbc_decrypt_combine_prepared": (ctypes.c_int, [_P, _S, _P, _P, _P, _S, _P, _P, _P, _P,
+                                                          _P]),
+        "hbrbc_decrypt_combine": (ctypes.c_int, [ctypes.c_char_p, _P, _S, ctypes.c_char_p,
+                                                 ctypes.c_char_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

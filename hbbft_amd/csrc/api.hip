@@ -2383,6 +2383,163 @@ int hbrbc_pairing_check(const uint8_t a[96], const uint8_t b[192], const uint8_t
     return HBRBC_OK;
 }
 
+// ---- decryption-share combine (pairing.hip): PublicKeySet::decrypt up to g --
+// workspace: projective points (limb-major), per-share status, coefficients,
+// per-group Lagrange status
+struct CombineWs {
+    uint32_t *pts;
+    uint8_t *pst, *coeffs, *lst;
+};
+
+static CombineWs combine_ws(void *workspace, size_t total, size_t groups) {
+    uint8_t *p = static_cast<uint8_t *>(workspace);
+    CombineWs w;
+    w.pts = reinterpret_cast<uint32_t *>(p);
+    p += round_up(g1_point_words(total) * 4, 256);
+    w.pst = p;
+    p += round_up(total, 256);
+    w.coeffs = p;
+    p += round_up(total * 32, 256);
+    w.lst = p;
+    (void)groups;
+    return w;
+}
+
+// The share count is the last entry of the device-side prefix sum: one
+// 4-byte read-back (and a wait for what precedes it on the stream) sizes the
+// per-share launches; the kernels themselves are queued without waiting.
+static int combine_total(const uint32_t *offsets, size_t groups, hipStream_t s, size_t *total) {
+    uint32_t v = 0;
+    HB_HIP(hipMemcpyAsync(&v, offsets + groups, sizeof v, hipMemcpyDeviceToHost, s));
+    HB_HIP(hipStreamSynchronize(s));
+    *total = v;
+    return HBRBC_OK;
+}
+
+static int have_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(HBRBC_E_NO_DEVICE, "no HIP device visible");
+    return HBRBC_OK;
+}
+
+static int lincomb_run(const void *a_prepared, size_t prepared_count, const int32_t *rows,
+                       const uint8_t *scalars, const uint32_t *offsets, size_t groups,
+                       size_t total, const uint8_t *lst, uint8_t *out96, uint8_t *out48,
+                       uint8_t *status_out, const CombineWs &w, hipStream_t s) {
+    const uint32_t *tab = static_cast<const uint32_t *>(a_prepared);
+    // the table's status bytes sit behind the coordinates of the count it was
+    // prepared with
+    const uint8_t *tst =
+        static_cast<const uint8_t *>(a_prepared) + round_up(g1_key_words(prepared_count) * 4, 256);
+    HB_HIP(launch_g1_scalar_mul(tab, tst, prepared_count, rows, scalars, total, w.pts, w.pst, s));
+    HB_HIP(launch_g1_reduce_encode(w.pts, w.pst, offsets, groups, total, lst, out96, out48,
+                                   status_out, s));
+    return HBRBC_OK;
+}
+
+size_t hbrbc_g1_combine_workspace_size(size_t total_shares, size_t groups) {
+    return round_up(g1_point_words(total_shares) * 4, 256) + round_up(total_shares, 256) +
+           round_up(total_shares * 32, 256) + round_up(groups, 256);
+}
+
+int hbrbc_lagrange_coeffs(const uint32_t *idx, const uint32_t *offsets, size_t groups,
+                          uint8_t *coeffs_out, uint8_t *status_out, void *stream) {
+    if (groups == 0) return HBRBC_OK;
+    if (!offsets || !status_out) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    size_t total = 0;
+    if (int rc = combine_total(offsets, groups, s, &total)) return rc;
+    if (total && (!idx || !coeffs_out)) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    HB_HIP(hipMemsetAsync(status_out, 0, groups, s));
+    HB_HIP(launch_lagrange(idx, offsets, groups, total, coeffs_out, status_out, s));
+    return HBRBC_OK;
+}
+
+int hbrbc_g1_lincomb_prepared(const void *a_prepared, size_t prepared_count, const int32_t *rows,
+                              const uint8_t *scalars, const uint32_t *offsets, size_t groups,
+                              uint8_t *out96, uint8_t *out48, uint8_t *status_out,
+                              void *workspace, void *stream) {
+    if (groups == 0) return HBRBC_OK;
+    if (!a_prepared || !offsets || !out96 || !out48 || !status_out || !workspace)
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    size_t total = 0;
+    if (int rc = combine_total(offsets, groups, s, &total)) return rc;
+    if (total && (!rows || !scalars)) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    return lincomb_run(a_prepared, prepared_count, rows, scalars, offsets, groups, total, nullptr,
+                       out96, out48, status_out, combine_ws(workspace, total, groups), s);
+}
+
+int hbrbc_decrypt_combine_prepared(const void *a_prepared, size_t prepared_count,
+                                   const int32_t *rows, const uint32_t *idx,
+                                   const uint32_t *offsets, size_t groups, uint8_t *out96,
+                                   uint8_t *out48, uint8_t *status_out, void *workspace,
+                                   void *stream) {
+    if (groups == 0) return HBRBC_OK;
+    if (!a_prepared || !offsets || !out96 || !out48 || !status_out || !workspace)
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    size_t total = 0;
+    if (int rc = combine_total(offsets, groups, s, &total)) return rc;
+    if (total && (!rows || !idx)) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    const CombineWs w = combine_ws(workspace, total, groups);
+    HB_HIP(hipMemsetAsync(w.lst, 0, groups, s));
+    HB_HIP(launch_lagrange(idx, offsets, groups, total, w.coeffs, w.lst, s));
+    return lincomb_run(a_prepared, prepared_count, rows, w.coeffs, offsets, groups, total, w.lst,
+                       out96, out48, status_out, w, s);
+}
+
+int hbrbc_decrypt_combine(const uint8_t *shares, const uint32_t *idx, size_t n, uint8_t out96[96],
+                          uint8_t out48[48]) {
+    if (!out96 || !out48 || (n && (!shares || !idx)))
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    // device block: shares | idx | rows | offsets | out96, out48, status |
+    // prepared table | workspace
+    const size_t o_idx = round_up(n * 96, 256), o_rows = o_idx + round_up(n * 4, 256);
+    const size_t o_off = o_rows + round_up(n * 4, 256), o_out = o_off + 256;
+    const size_t o_tab = o_out + 256, o_ws = o_tab + hbrbc_g1_prepared_size(n);
+    const size_t bytes = o_ws + hbrbc_g1_combine_workspace_size(n, 1);
+    uint8_t *dev = nullptr;
+    HB_HIP(hipMalloc(&dev, bytes));
+    std::vector<uint8_t> host(o_out, 0);
+    if (n) {
+        memcpy(host.data(), shares, n * 96);
+        memcpy(host.data() + o_idx, idx, n * 4);
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const int32_t r = (int32_t)i;
+        memcpy(host.data() + o_rows + 4 * i, &r, 4);
+    }
+    const uint32_t offs[2] = {0, (uint32_t)n};
+    memcpy(host.data() + o_off, offs, sizeof offs);
+    uint8_t out[256] = {0};
+    int rc = HBRBC_OK;
+    hipError_t e = hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = hbrbc_g1_prepare(dev, n, dev + o_tab, nullptr);
+        if (rc == HBRBC_OK)
+            rc = hbrbc_decrypt_combine_prepared(
+                dev + o_tab, n, reinterpret_cast<const int32_t *>(dev + o_rows),
+                reinterpret_cast<const uint32_t *>(dev + o_idx),
+                reinterpret_cast<const uint32_t *>(dev + o_off), 1, dev + o_out, dev + o_out + 96,
+                dev + o_out + 144, dev + o_ws, nullptr);
+        if (rc == HBRBC_OK) e = hipMemcpy(out, dev + o_out, 145, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(dev);
+    if (e != hipSuccess) return fail(HBRBC_E_DEVICE, "decrypt combine: %s", hipGetErrorString(e));
+    if (rc != HBRBC_OK) return rc;
+    if (out[144] == 3) return fail(HBRBC_E_INVALID_ARG, "duplicate share index");
+    if (out[144] == 2) return fail(HBRBC_E_INVALID_ARG, "invalid curve point");
+    memcpy(out96, out, 96);
+    memcpy(out48, out + 96, 48);
+    return HBRBC_OK;
+}
+
 // ---- f2: the Broadcast state machine, batched (sim.hip) -------------------
 size_t hbrbc_sm_state_bytes(size_t n, size_t roots) { return sm_state_bytes(n, roots); }
 

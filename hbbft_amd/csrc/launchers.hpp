@@ -269,6 +269,18 @@ hipError_t launch_pairing_miller_prepared_keys(const uint8_t *g1_a, const uint32
 hipError_t launch_pairing_final(const uint32_t *ws, size_t n_miller, size_t n_out, int per_out,
                                 const uint8_t *status, uint8_t *gt_out, uint8_t *ok_out,
                                 hipStream_t s);
+// decryption-share combine (pairing.hip): Lagrange coefficients, [k] P per
+// share from a g1_prepare table into a limb-major workspace of
+// g1_point_words(total) words, per-group sum and encodings
+size_t g1_point_words(size_t shares);
+hipError_t launch_lagrange(const uint32_t *idx, const uint32_t *offsets, size_t groups,
+                           size_t total, uint8_t *coeffs, uint8_t *status, hipStream_t s);
+hipError_t launch_g1_scalar_mul(const uint32_t *tab, const uint8_t *tst, size_t nprep,
+                                const int32_t *rows, const uint8_t *scalars, size_t total,
+                                uint32_t *ws, uint8_t *pst, hipStream_t s);
+hipError_t launch_g1_reduce_encode(const uint32_t *ws, const uint8_t *pst, const uint32_t *offsets,
+                                   size_t groups, size_t total, const uint8_t *lst, uint8_t *out96,
+                                   uint8_t *out48, uint8_t *status, hipStream_t s);
 
 hipError_t configure_kernels();
 

@@ -1316,6 +1316,458 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G
     kst[q] = (uint8_t)st;
 }
 
+// ------------------------------------------------- decryption-share combine
+// ThresholdDecrypt's output step (threshold_decrypt.rs:232-252, try_output):
+// `public_key_set().decrypt(shares, &ct)` is, in threshold_crypto, the
+// Lagrange interpolation at 0 of the shares in G1,
+//
+//     g = sum_i lambda_i share_i,   x_i = node index + 1,
+//     lambda_i = prod_{j != i} x_j / (x_j - x_i)   in Fr,
+//
+// followed by xor_with_hash(g, V) (the caller's).  Three kernels: the
+// coefficients (one lane per share, Fr arithmetic), [lambda_i] share_i (one
+// lane per share, the shares read decoded and checked from a g1_prepare
+// table), and the sum of each group with its two encodings (one lane per
+// group).  Groups are ragged: offsets[g] .. offsets[g + 1] of the flat share
+// arrays.  Every read through `offsets` is clamped to the share count, so a
+// malformed prefix sum gives wrong answers, never an out-of-bounds access.
+
+// Fr: the 255-bit scalar field, 8 x 32-bit limbs, Montgomery form R = 2^256.
+constexpr int NR = 8;
+struct Fr { uint32_t l[NR]; };
+
+DEV void fr_set(Fr &r, const uint32_t (&v)[NR]) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i) r.l[i] = v[i];
+}
+
+DEV bool fr_is_zero(const Fr &a) {
+    uint32_t t = 0;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) t |= a.l[i];
+    return t == 0;
+}
+
+// a < r (canonical)
+DEV bool fr_is_canonical(const Fr &a) {
+    uint32_t br = 0;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) (void)subb(a.l[i], kFrR[i], br, &br);
+    return br != 0;
+}
+
+DEV void fr_sub(Fr &r, const Fr &a, const Fr &b) {
+    uint32_t t[NR];
+    uint32_t br = 0;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) t[i] = subb(a.l[i], b.l[i], br, &br);
+    const uint32_t mask = 0u - br;  // add r back on borrow
+    uint32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) r.l[i] = addc(t[i], kFrR[i] & mask, c, &c);
+}
+
+// Montgomery product a*b*2^-256 mod r (CIOS over 32-bit limbs; inputs < r,
+// the sum stays below 2r < 2^256 and is reduced once)
+DEV void fr_mul(Fr &r, const Fr &a, const Fr &b) {
+    uint32_t t[NR + 1];
+#pragma unroll
+    for (int i = 0; i <= NR; ++i) t[i] = 0;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        uint64_t c = 0;
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            c += (uint64_t)a.l[j] * b.l[i] + t[j];
+            t[j] = (uint32_t)c;
+            c >>= 32;
+        }
+        c += t[NR];
+        t[NR] = (uint32_t)c;
+        const uint32_t t9 = (uint32_t)(c >> 32);
+        const uint32_t m = t[0] * kFrInv32;
+        c = (uint64_t)m * kFrR[0] + t[0];   // low word becomes 0
+        c >>= 32;
+#pragma unroll
+        for (int j = 1; j < NR; ++j) {
+            c += (uint64_t)m * kFrR[j] + t[j];
+            t[j - 1] = (uint32_t)c;
+            c >>= 32;
+        }
+        c += t[NR];
+        t[NR - 1] = (uint32_t)c;
+        t[NR] = t9 + (uint32_t)(c >> 32);
+    }
+    uint32_t s[NR];
+    uint32_t br = 0;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) s[i] = subb(t[i], kFrR[i], br, &br);
+    const bool keep = br && !t[NR];   // t < r
+#pragma unroll
+    for (int i = 0; i < NR; ++i) r.l[i] = keep ? t[i] : s[i];
+}
+
+// canonical 64-bit value -> Montgomery form
+DEV void fr_from_u64(Fr &r, uint64_t v) {
+    Fr a, r2;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) a.l[i] = 0;
+    a.l[0] = (uint32_t)v;
+    a.l[1] = (uint32_t)(v >> 32);
+    fr_set(r2, kFrR2);
+    fr_mul(r, a, r2);
+}
+
+// a^(r-2) (Fermat); once per coefficient
+NOINL void fr_inv(Fr &r, const Fr &a) {
+    Fr acc, base = a;
+    fr_set(acc, kFrOne);
+    for (int w = 0; w < NR; ++w) {
+        uint32_t e = kFrMinus2[w];
+        for (int b = 0; b < 32; ++b) {
+            if (e & 1u) fr_mul(acc, acc, base);
+            fr_mul(base, base, base);
+            e >>= 1;
+        }
+    }
+    r = acc;
+}
+
+// 32 big-endian bytes <-> limbs (little-endian words), canonical form
+DEV void fr_load_be32(Fr &r, const uint8_t *src) {
+#pragma unroll
+    for (int w = 0; w < NR; ++w) {
+        const uint8_t *q = src + 28 - 4 * w;
+        r.l[w] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
+    }
+}
+
+DEV void fr_store_be32(uint8_t *dst, const Fr &a) {
+#pragma unroll
+    for (int w = 0; w < NR; ++w) {
+        const uint32_t v = a.l[NR - 1 - w];
+        dst[4 * w + 0] = (uint8_t)(v >> 24);
+        dst[4 * w + 1] = (uint8_t)(v >> 16);
+        dst[4 * w + 2] = (uint8_t)(v >> 8);
+        dst[4 * w + 3] = (uint8_t)v;
+    }
+}
+
+// Group statuses of the combine: CB_INF = ok and the sum is the point at
+// infinity; CB_DUP = two equal node indices (the crate's DuplicateEntry)
+enum { CB_OK = 0, CB_INF = 1, CB_BAD = 2, CB_DUP = 3 };
+
+// the shares [b, e) of group g, clamped to the share count
+DEV void group_range(const uint32_t *offsets, size_t g, size_t total, size_t &b, size_t &e) {
+    const size_t hi = offsets[g + 1], lo = offsets[g];
+    e = hi < total ? hi : total;
+    b = lo < e ? lo : e;
+}
+
+// Kernel: one lane per (group, share).  Share j of group g (found by binary
+// search in the prefix sum) forms x = idx + 1 in 64 bits (idx = 0xFFFFFFFF is
+// x = 2^32, not 0) and writes lambda_j as 32 canonical big-endian bytes.  A
+// zero denominator is a repeated index: status 3 for the group (the caller
+// clears `status` before the launch; only failing lanes write), zero bytes
+// for the coefficient.
+__global__ __launch_bounds__(kPairBlock) void lagrange_kernel(
+    const uint32_t *__restrict__ idx, const uint32_t *__restrict__ offsets, size_t groups,
+    size_t total, uint8_t *__restrict__ coeffs, uint8_t *__restrict__ status) {
+    const size_t j = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (j >= total) return;
+    uint8_t *dst = coeffs + 32 * j;
+    size_t lo = 0, hi = groups;   // the first group starting past j
+    while (lo < hi) {
+        const size_t mid = (lo + hi) >> 1;
+        if (offsets[mid] <= j) lo = mid + 1; else hi = mid;
+    }
+    size_t b = 0, e = 0;
+    if (lo > 0) group_range(offsets, lo - 1, total, b, e);
+    Fr lam;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) lam.l[i] = 0;
+    if (j >= b && j < e) {   // else: malformed offsets, share in no group
+        Fr xi, num, den;
+        fr_from_u64(xi, (uint64_t)idx[j] + 1);
+        fr_set(num, kFrOne);
+        fr_set(den, kFrOne);
+        for (size_t k = b; k < e; ++k) {
+            if (k == j) continue;
+            Fr xk, d;
+            fr_from_u64(xk, (uint64_t)idx[k] + 1);
+            fr_sub(d, xk, xi);
+            fr_mul(num, num, xk);
+            fr_mul(den, den, d);
+        }
+        if (fr_is_zero(den)) {
+            status[lo - 1] = CB_DUP;
+        } else {
+            Fr one;
+            fr_inv(den, den);
+            fr_mul(lam, num, den);
+#pragma unroll
+            for (int i = 0; i < NR; ++i) one.l[i] = 0;
+            one.l[0] = 1;
+            fr_mul(lam, lam, one);   // out of Montgomery form
+        }
+    }
+    fr_store_be32(dst, lam);
+}
+
+// Projective points between the kernels: limb-major like store_f12, word w of
+// share j at ws[w * n + j] (X, Y, Z: kPtWords words).
+constexpr int kPtWords = 3 * NL;
+
+DEV void store_pt(uint32_t *ws, size_t n, size_t j, const PtProj<Fp> &p) {
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(&p);
+#pragma unroll 4
+    for (int w = 0; w < kPtWords; ++w) ws[(size_t)w * n + j] = src[w];
+}
+
+DEV void load_pt(PtProj<Fp> &p, const uint32_t *ws, size_t n, size_t j) {
+    uint32_t *dst = reinterpret_cast<uint32_t *>(&p);
+#pragma unroll 4
+    for (int w = 0; w < kPtWords; ++w) dst[w] = ws[(size_t)w * n + j];
+}
+
+DEV void pt_identity(PtProj<Fp> &p) {
+    fp_zero(p.x);
+    fp_set(p.y, kOne);
+    fp_zero(p.z);
+}
+
+// HB_G1_GLV: the scalar multiplication through the endomorphism (1) or plain
+// double-and-add over 255 bits (0) (A/B).  phi(P) = (beta x, y)
+// = -[x^2] P on G1 (g1_in_subgroup above), so with k = k1 + k2 x^2 (k1 < x^2
+// by plain long division; k2 < 2^128 because k < r = x^4 - x^2 + 1)
+//     [k] P = [k1] P + [k2] Q,   Q = [x^2] P = (beta x, -y),
+// two 128-bit halves on one doubling chain.  Per bit the lane adds P, Q or
+// P + Q, chosen by the two bits, through one call of the projective addition
+// with a selected operand: lanes with different bits do not serialise three
+// additions, and a wave pays 128 doublings and 128 additions where the plain
+// loop with per-lane scalars pays 255 and nearly 255.
+#ifndef HB_G1_GLV
+#define HB_G1_GLV 1
+#endif
+
+DEV void fr_shl1(Fr &k) {
+#pragma unroll
+    for (int i = NR - 1; i > 0; --i) k.l[i] = (k.l[i] << 1) | (k.l[i - 1] >> 31);
+    k.l[0] <<= 1;
+}
+
+#if HB_G1_GLV
+// k = k1 + k2 x^2, k < r: bit-serial long division by the 128-bit x^2 (a few
+// thousand integer operations against a million in the curve arithmetic)
+DEV void glv_split(Fr k, uint64_t &k1hi, uint64_t &k1lo, uint64_t &k2hi, uint64_t &k2lo) {
+    uint64_t rhi = 0, rlo = 0, qhi = 0, qlo = 0;
+    fr_shl1(k);   // bit 254 to the top
+    for (int b = 254; b >= 0; --b) {
+        const uint64_t bit = k.l[NR - 1] >> 31;
+        fr_shl1(k);
+        const uint64_t carry = rhi >> 63;   // the remainder doubled may reach 2^128
+        rhi = (rhi << 1) | (rlo >> 63);
+        rlo = (rlo << 1) | bit;
+        const bool ge = carry || rhi > kXSqHi || (rhi == kXSqHi && rlo >= kXSqLo);
+        if (ge) {
+            const uint64_t borrow = rlo < kXSqLo;
+            rlo -= kXSqLo;
+            rhi -= kXSqHi + borrow;
+        }
+        qhi = (qhi << 1) | (qlo >> 63);
+        qlo = (qlo << 1) | (ge ? 1u : 0u);
+    }
+    k1hi = rhi;
+    k1lo = rlo;
+    k2hi = qhi;
+    k2lo = qlo;
+}
+#endif
+
+// p <- p + q, both projective (Renes-Costello-Batina algorithm 7 with a = 0:
+// complete, E(Fp) has odd order)
+NOINL void pt_add_proj(PtProj<Fp> &p, const PtProj<Fp> &q) {
+    Fp t0, t1, t2, t3, t4, x3, y3, z3;
+    fp_mul(t0, p.x, q.x);
+    fp_mul(t1, p.y, q.y);
+    fp_mul(t2, p.z, q.z);
+    fp_add(t3, p.x, p.y);
+    fp_add(t4, q.x, q.y);
+    fp_mul(t3, t3, t4);
+    fp_add(t4, t0, t1);
+    fp_sub(t3, t3, t4);             // X1 Y2 + X2 Y1
+    fp_add(t4, p.y, p.z);
+    fp_add(x3, q.y, q.z);
+    fp_mul(t4, t4, x3);
+    fp_add(x3, t1, t2);
+    fp_sub(t4, t4, x3);             // Y1 Z2 + Y2 Z1
+    fp_add(x3, p.x, p.z);
+    fp_add(y3, q.x, q.z);
+    fp_mul(x3, x3, y3);
+    fp_add(y3, t0, t2);
+    fp_sub(y3, x3, y3);             // X1 Z2 + X2 Z1
+    fp_add(x3, t0, t0);
+    fp_add(t0, x3, t0);
+    fe_mul_b3(t2, t2);
+    fp_add(z3, t1, t2);
+    fp_sub(t1, t1, t2);
+    fe_mul_b3(y3, y3);
+    fp_mul(x3, t4, y3);
+    fp_mul(t2, t3, t1);
+    fp_sub(x3, t2, x3);
+    fp_mul(y3, y3, t0);
+    fp_mul(t1, t1, z3);
+    fp_add(y3, t1, y3);
+    fp_mul(t0, t0, t3);
+    fp_mul(z3, z3, t4);
+    fp_add(p.z, z3, t0);
+    p.x = x3;
+    p.y = y3;
+}
+
+// Kernel: one lane per share, [k_j] P_j (HB_G1_GLV above; the plain form is
+// double-and-add over the 255 bits of k).  The complete formulas take the
+// identity as a start value and any intermediate sum, so there is no
+// leading-bit search and no special case.
+// P_j = row rows[j] of a g1_prepare table of `nprep` points, k_j = 32
+// big-endian bytes.  k = 0 and a table entry at infinity give the identity;
+// k >= r, an invalid table entry and a row outside the table give pst = 2.
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_scalar_mul_kernel(
+    const uint32_t *__restrict__ tab, const uint8_t *__restrict__ tst, size_t nprep,
+    const int32_t *__restrict__ rows, const uint8_t *__restrict__ scalars, size_t total,
+    uint32_t *__restrict__ ws, uint8_t *__restrict__ pst) {
+    const size_t j = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (j >= total) return;
+    const int32_t row = rows[j];
+    // a row past the table is an invalid input, never an out-of-bounds read
+    int st = (row >= 0 && (size_t)row < nprep) ? tst[row] : PT_BAD;
+    Fr k;
+    fr_load_be32(k, scalars + 32 * j);
+    if (!fr_is_canonical(k)) st = PT_BAD;
+    PtProj<Fp> acc;
+    pt_identity(acc);
+    if (st == PT_OK) {
+        Fp x, y;
+        load_g1_key(tab + (size_t)row * kG1KeyWords, x, y);
+#if HB_G1_GLV
+        uint64_t k1hi, k1lo, k2hi, k2lo;
+        glv_split(k, k1hi, k1lo, k2hi, k2lo);
+        PtProj<Fp> pp, qq, tt;   // P, Q = (beta x, -y), P + Q
+        pp.x = x;
+        pp.y = y;
+        fp_set(pp.z, kOne);
+        fp_set(qq.x, kBeta);
+        fp_mul(qq.x, qq.x, x);
+        fp_neg(qq.y, y);
+        qq.z = pp.z;
+        tt = pp;
+        pt_add_proj(tt, qq);
+        const uint32_t *wp = reinterpret_cast<const uint32_t *>(&pp);
+        const uint32_t *wq = reinterpret_cast<const uint32_t *>(&qq);
+        const uint32_t *wt = reinterpret_cast<const uint32_t *>(&tt);
+        for (int b = 127; b >= 0; --b) {
+            pt_dbl(acc);
+            const unsigned sel = (unsigned)(k1hi >> 63) | ((unsigned)(k2hi >> 63) << 1);
+            k1hi = (k1hi << 1) | (k1lo >> 63);
+            k1lo <<= 1;
+            k2hi = (k2hi << 1) | (k2lo >> 63);
+            k2lo <<= 1;
+            if (sel) {
+                PtProj<Fp> op;
+                uint32_t *wo = reinterpret_cast<uint32_t *>(&op);
+#pragma unroll
+                for (int w = 0; w < kPtWords; ++w)
+                    wo[w] = sel == 1 ? wp[w] : (sel == 2 ? wq[w] : wt[w]);
+                pt_add_proj(acc, op);
+            }
+        }
+#else
+        // k < r < 2^255: bit 254 moves to the top of the highest limb, then
+        // the scalar shifts left one bit per step (no indexed register reads)
+        fr_shl1(k);
+        for (int b = 254; b >= 0; --b) {
+            pt_dbl(acc);
+            if (k.l[NR - 1] >> 31) pt_add_affine(acc, x, y);
+            fr_shl1(k);
+        }
+#endif
+    }
+    pst[j] = (uint8_t)(st == PT_BAD ? PT_BAD : PT_OK);
+    store_pt(ws, total, j, acc);
+}
+
+// 48 big-endian bytes of a canonical (non-Montgomery) value, `flags` or-ed
+// into byte 0
+DEV void store_be48_raw(uint8_t *dst, const Fp &c, uint8_t flags) {
+#pragma unroll
+    for (int w = 0; w < NL; ++w) {
+        const uint32_t v = c.l[NL - 1 - w];
+        dst[4 * w + 0] = (uint8_t)(v >> 24);
+        dst[4 * w + 1] = (uint8_t)(v >> 16);
+        dst[4 * w + 2] = (uint8_t)(v >> 8);
+        dst[4 * w + 3] = (uint8_t)v;
+    }
+    dst[0] |= flags;
+}
+
+// Kernel: one lane per group.  Sums the group's projective points, converts
+// to affine with one inversion and writes the uncompressed encoding (96
+// bytes, x || y) and the compressed one (48 bytes: x with 0x80 set, 0x20 set
+// iff y > p - y as integers; infinity = 0xC0 and zeros) -- zkcrypto's
+// G1Uncompressed / G1Compressed.  status: 0 ok, 1 ok and the sum is the
+// point at infinity, 2 an invalid share / scalar / row in the group, 3 a
+// repeated index (`lst`, from lagrange_kernel; may be null); for 2 and 3
+// both outputs are zero bytes.  An empty group is the empty sum: status 1.
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_reduce_encode_kernel(
+    const uint32_t *__restrict__ ws, const uint8_t *__restrict__ pst,
+    const uint32_t *__restrict__ offsets, size_t groups, size_t total,
+    const uint8_t *__restrict__ lst, uint8_t *__restrict__ out96, uint8_t *__restrict__ out48,
+    uint8_t *__restrict__ status) {
+    const size_t g = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (g >= groups) return;
+    size_t b, e;
+    group_range(offsets, g, total, b, e);
+    int st = (lst && lst[g] == CB_DUP) ? CB_DUP : CB_OK;
+    if (st == CB_OK)
+        for (size_t k = b; k < e; ++k)
+            if (pst[k] == PT_BAD) st = CB_BAD;
+    uint8_t *o96 = out96 + 96 * g, *o48 = out48 + 48 * g;
+    for (int i = 0; i < 96; ++i) o96[i] = 0;
+    for (int i = 0; i < 48; ++i) o48[i] = 0;
+    if (st == CB_OK) {
+        PtProj<Fp> acc, q;
+        pt_identity(acc);
+        for (size_t k = b; k < e; ++k) {
+            load_pt(q, ws, total, k);
+            pt_add_proj(acc, q);
+        }
+        if (fp_is_zero(acc.z)) {
+            st = CB_INF;
+            o96[0] = 0x40;
+            o48[0] = 0xC0;
+        } else {
+            Fp zi, x, y, ny;
+            fp_inv(zi, acc.z);
+            fp_mul(x, acc.x, zi);
+            fp_mul(y, acc.y, zi);
+            from_mont(x, x);
+            from_mont(y, y);
+            // p - y against y, most significant limb first
+            uint32_t br = 0;
+#pragma unroll
+            for (int i = 0; i < NL; ++i) ny.l[i] = subb(kP[i], y.l[i], br, &br);
+            int cmp = 0;   // sign of y - (p - y)
+#pragma unroll
+            for (int i = NL - 1; i >= 0; --i)
+                if (cmp == 0 && y.l[i] != ny.l[i]) cmp = y.l[i] > ny.l[i] ? 1 : -1;
+            store_be48_raw(o96, x, 0);
+            store_be48_raw(o96 + 48, y, 0);
+            store_be48_raw(o48, x, (uint8_t)(0x80 | (cmp > 0 ? 0x20 : 0)));
+        }
+    }
+    status[g] = (uint8_t)st;
+}
+
 // One lane per check e(a, b) == e(c, d) with b, d prepared (points ib[i],
 // id[i] of the table): g1 holds a, c at rows 2i, 2i+1.  Lanes of a wave
 // checking against the same points read the same lines (one cache line
@@ -1549,6 +2001,37 @@ hipError_t launch_g1_prepare(const uint8_t *g1, size_t count, uint32_t *keys, ui
     const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
     hipLaunchKernelGGL(g1_prepare_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g1, count, keys,
                        kst);
+    return hipGetLastError();
+}
+
+size_t g1_point_words(size_t shares) { return shares * (size_t)kPtWords; }
+
+hipError_t launch_lagrange(const uint32_t *idx, const uint32_t *offsets, size_t groups,
+                           size_t total, uint8_t *coeffs, uint8_t *status, hipStream_t s) {
+    if (total == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((total + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(lagrange_kernel, dim3(blocks), dim3(kPairBlock), 0, s, idx, offsets, groups,
+                       total, coeffs, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_g1_scalar_mul(const uint32_t *tab, const uint8_t *tst, size_t nprep,
+                                const int32_t *rows, const uint8_t *scalars, size_t total,
+                                uint32_t *ws, uint8_t *pst, hipStream_t s) {
+    if (total == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((total + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g1_scalar_mul_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab, tst, nprep,
+                       rows, scalars, total, ws, pst);
+    return hipGetLastError();
+}
+
+hipError_t launch_g1_reduce_encode(const uint32_t *ws, const uint8_t *pst, const uint32_t *offsets,
+                                   size_t groups, size_t total, const uint8_t *lst, uint8_t *out96,
+                                   uint8_t *out48, uint8_t *status, hipStream_t s) {
+    if (groups == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((groups + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g1_reduce_encode_kernel, dim3(blocks), dim3(kPairBlock), 0, s, ws, pst,
+                       offsets, groups, total, lst, out96, out48, status);
     return hipGetLastError();
 }
 

@@ -15,6 +15,15 @@ ciphertexts, so the pairing checks come in batches of N^2 per node; this
 module runs them through `hbrbc_pairing_check_batch` (hbbft_amd/csrc/
 pairing.hip): one Miller loop per lane, one final exponentiation per check.
 
+Once more than `num_faulty` valid shares are in, `try_output` (lines 232-252)
+calls `public_key_set().decrypt(shares, &ct)`: the Lagrange interpolation at 0
+of the shares in G1, g = sum lambda_i share_i, followed by xor_with_hash(g, V).
+`decrypt_combine_prepared` computes g for batches of ciphertexts from the same
+prepared table the checks read, so the verified shares never leave the device;
+`decrypt_shares_grouped` is the two steps in one call.  xor_with_hash (like
+hash_g1_g2) stays with the caller; it hashes the compressed encoding of g,
+which comes back beside the uncompressed one.
+
 Points are the crate's uncompressed encodings (G1: 96 bytes, G2: 192 bytes,
 big-endian; see include/hbrbc.h).  There is no CPU fallback: without the
 library or a GPU the calls raise `HbrbcUnavailable`.
@@ -33,6 +42,11 @@ G1_ONE = bytes.fromhex(
     "08b3f481e3aaa0f1a09e30ed741d8ae4fcf5e095d5d00af600db18cb2c04b3edd03cc744a2888ae40caa232946c5e7e1")
 
 CHECK_OK, CHECK_FAIL, CHECK_INVALID = 1, 0, 2
+
+G1_COMPRESSED_BYTES = 48
+FR_BYTES = 32
+# per-group status of the combine entries
+COMBINE_OK, COMBINE_INFINITY, COMBINE_INVALID, COMBINE_DUPLICATE = 0, 1, 2, 3
 
 
 def _torch():
@@ -189,10 +203,21 @@ def verify_decryption_shares_grouped(ciphertexts, shares, device=0):
     received shares are decoded in a launch of their own; shares are grouped
     by ciphertext so a wave shares its lines.  Returns bools in the order of
     `shares`."""
-    import numpy as np
-    torch = _torch()
     if not shares:
         return []
+    okh, order, _ = _verify_grouped(ciphertexts, shares, device)
+    out = [False] * len(shares)
+    for r, i in enumerate(order):
+        out[i] = okh[r] == CHECK_OK
+    return out
+
+
+def _verify_grouped(ciphertexts, shares, device):
+    """The work of verify_decryption_shares_grouped: returns (outcomes by
+    table row, the input position of each row, the g1_prepare table of the
+    shares -- row r holds share order[r])."""
+    import numpy as np
+    torch = _torch()
     dev = "cuda:%d" % device
     g2 = np.empty((2 * len(ciphertexts), G2_BYTES), np.uint8)
     for j, (h, w) in enumerate(ciphertexts):
@@ -234,11 +259,200 @@ def verify_decryption_shares_grouped(ciphertexts, shares, device=0):
     ok = pairing_check_prepared_pts(sprep, len(shares), ktab, len(key_ids),
                                     torch.from_numpy(ic).to(dev), prep, 2 * len(ciphertexts),
                                     torch.from_numpy(ib).to(dev), torch.from_numpy(ib + 1).to(dev))
-    okh = ok.cpu().tolist()
-    out = [False] * len(shares)
+    return ok.cpu().tolist(), order, sprep
+
+
+def combine_workspace(total_shares, groups, device=0):
+    """Device workspace for combining `total_shares` shares in `groups` groups."""
+    torch = _torch()
+    n = lib().hbrbc_g1_combine_workspace_size(total_shares, groups)
+    return torch.empty(max(n, 1), dtype=torch.uint8, device="cuda:%d" % device)
+
+
+def _ragged(offsets, *per_share):
+    """Checks a ragged batch: offsets int32 [groups + 1], a prefix sum ending at
+    the length of every per-share tensor (read back once: the C entries size
+    their launches by it).  Returns (groups, total)."""
+    torch = _torch()
+    assert offsets.dtype == torch.int32 and offsets.dim() == 1 and offsets.numel() >= 1
+    assert offsets.is_contiguous()
+    total = per_share[0].shape[0]
+    for t in per_share:
+        assert t.shape[0] == total and t.is_contiguous() and t.device == offsets.device
+    assert int(offsets[-1]) == total, (int(offsets[-1]), total)
+    return offsets.numel() - 1, total
+
+
+def lagrange_coeffs(idx, offsets, stream=None):
+    """Lagrange coefficients at 0 of ragged groups of node indices: idx int32
+    [total] (the bits of an unsigned 32-bit index; x = idx + 1), offsets int32
+    [groups + 1].  Returns (coeffs uint8 [total, 32], big-endian and canonical;
+    status uint8 [groups]: 0 ok, 3 a repeated index)."""
+    torch = _torch()
+    assert idx.dtype == torch.int32 and idx.dim() == 1
+    groups, total = _ragged(offsets, idx)
+    coeffs = torch.empty((total, FR_BYTES), dtype=torch.uint8, device=idx.device)
+    st = torch.empty((groups,), dtype=torch.uint8, device=idx.device)
+    _check(lib().hbrbc_lagrange_coeffs(idx.data_ptr(), offsets.data_ptr(), groups,
+                                       coeffs.data_ptr(), st.data_ptr(),
+                                       _stream(idx.device, stream)))
+    return coeffs, st
+
+
+def _combine_outputs(groups, device):
+    torch = _torch()
+    return (torch.empty((groups, G1_BYTES), dtype=torch.uint8, device=device),
+            torch.empty((groups, G1_COMPRESSED_BYTES), dtype=torch.uint8, device=device),
+            torch.empty((groups,), dtype=torch.uint8, device=device))
+
+
+def g1_lincomb_prepared(a_prep, prepared_count, rows, scalars, offsets, ws=None, stream=None):
+    """Per group sum_j scalars[j] * T[rows[j]] over T = a_prep, a g1_prepare
+    table of exactly `prepared_count` points: rows int32 [total], scalars uint8
+    [total, 32] (big-endian, < r), offsets int32 [groups + 1].  Returns (out96
+    uint8 [groups, 96], out48 uint8 [groups, 48] compressed, status uint8
+    [groups]: 0 ok, 1 infinity, 2 invalid input; failed groups are zero bytes)."""
+    torch = _torch()
+    assert a_prep.numel() == lib().hbrbc_g1_prepared_size(prepared_count)
+    assert rows.dtype == torch.int32 and rows.dim() == 1
+    assert scalars.dtype == torch.uint8 and scalars.shape == (rows.shape[0], FR_BYTES)
+    groups, total = _ragged(offsets, rows, scalars)
+    assert a_prep.device == rows.device
+    out96, out48, st = _combine_outputs(groups, rows.device)
+    if ws is None:
+        ws = combine_workspace(total, groups, rows.device.index)
+    assert ws.numel() >= lib().hbrbc_g1_combine_workspace_size(total, groups)
+    _check(lib().hbrbc_g1_lincomb_prepared(
+        a_prep.data_ptr(), prepared_count, rows.data_ptr(), scalars.data_ptr(), offsets.data_ptr(),
+        groups, out96.data_ptr(), out48.data_ptr(), st.data_ptr(), ws.data_ptr(),
+        _stream(rows.device, stream)))
+    return out96, out48, st
+
+
+def decrypt_combine_prepared(a_prep, prepared_count, rows, idx, offsets, ws=None, stream=None):
+    """`PublicKeySet::decrypt` up to g for ragged groups of shares: share j is
+    row rows[j] of a_prep (a g1_prepare table of exactly `prepared_count`
+    points) and comes from node idx[j]; rows, idx int32 [total], offsets int32
+    [groups + 1].  Returns (out96, out48, status) as g1_lincomb_prepared, with
+    status 3 for a group that repeats an index."""
+    torch = _torch()
+    assert a_prep.numel() == lib().hbrbc_g1_prepared_size(prepared_count)
+    assert rows.dtype == torch.int32 and rows.dim() == 1
+    assert idx.dtype == torch.int32 and idx.dim() == 1
+    groups, total = _ragged(offsets, rows, idx)
+    assert a_prep.device == rows.device
+    out96, out48, st = _combine_outputs(groups, rows.device)
+    if ws is None:
+        ws = combine_workspace(total, groups, rows.device.index)
+    assert ws.numel() >= lib().hbrbc_g1_combine_workspace_size(total, groups)
+    _check(lib().hbrbc_decrypt_combine_prepared(
+        a_prep.data_ptr(), prepared_count, rows.data_ptr(), idx.data_ptr(), offsets.data_ptr(),
+        groups, out96.data_ptr(), out48.data_ptr(), st.data_ptr(), ws.data_ptr(),
+        _stream(rows.device, stream)))
+    return out96, out48, st
+
+
+def _u32_tensor(values, dev):
+    """Unsigned 32-bit values as the int32 tensor the wrappers take."""
+    import numpy as np
+    return _torch().from_numpy(np.asarray(values, dtype=np.uint32).view(np.int32)).to(dev)
+
+
+def _combine_results(out96, out48, st):
+    o96, o48, sth = out96.cpu().numpy(), out48.cpu().numpy(), st.cpu().tolist()
+    return [(bytes(o96[g]), bytes(o48[g])) if s in (COMBINE_OK, COMBINE_INFINITY) else None
+            for g, s in enumerate(sth)]
+
+
+def combine_decryption_shares(groups, device=0):
+    """`PublicKeySet::decrypt` up to g for host bytes: groups = [[(node index,
+    share G1)]].  Returns per group (g uncompressed 96 bytes, g compressed 48
+    bytes), or None for a group with an invalid share or a repeated index."""
+    import numpy as np
+    torch = _torch()
+    lib()
+    if not groups:
+        return []
+    flat = [item for grp in groups for item in grp]
+    for _, share in flat:
+        if len(share) != G1_BYTES:
+            raise ValueError("share of %d bytes, expected %d" % (len(share), G1_BYTES))
+    total = len(flat)
+    if not torch.cuda.is_available():
+        raise HbrbcUnavailable("no HIP device visible")
+    dev = "cuda:%d" % device
+    g1 = np.empty((total, G1_BYTES), np.uint8)
+    for r, (_, share) in enumerate(flat):
+        g1[r] = np.frombuffer(share, np.uint8)
+    offs = np.zeros(len(groups) + 1, np.int32)
+    offs[1:] = np.cumsum([len(grp) for grp in groups])
+    tab = g1_prepare(torch.from_numpy(g1).to(dev))
+    out = decrypt_combine_prepared(tab, total, torch.arange(total, dtype=torch.int32, device=dev),
+                                   _u32_tensor([i for i, _ in flat], dev),
+                                   torch.from_numpy(offs).to(dev))
+    return _combine_results(*out)
+
+
+def decrypt_combine(shares):
+    """Per-call shim: one group [(node index, share G1)] of host bytes through
+    hbrbc_decrypt_combine (one device round trip).  Returns (g96, g48); raises
+    RseError(InvalidArgument) on an invalid share or a repeated index."""
+    import numpy as np
+    for _, share in shares:
+        if len(share) != G1_BYTES:
+            raise ValueError("share of %d bytes, expected %d" % (len(share), G1_BYTES))
+    idx = np.asarray([i for i, _ in shares], dtype=np.uint32)
+    o96 = ctypes.create_string_buffer(G1_BYTES)
+    o48 = ctypes.create_string_buffer(G1_COMPRESSED_BYTES)
+    _check(lib().hbrbc_decrypt_combine(b"".join(bytes(s) for _, s in shares), idx.ctypes.data,
+                                       len(shares), o96, o48))
+    return o96.raw, o48.raw
+
+
+def decrypt_shares_grouped(ciphertexts, shares, threshold, device=0):
+    """ThresholdDecrypt's share handling for many ciphertexts: ciphertexts =
+    [(hash G2, W G2)], shares = [(ciphertext index, node index, share G1,
+    pk_share G1)].  The shares are prepared and verified as in
+    verify_decryption_shares_grouped; then each ciphertext combines its first
+    `threshold + 1` valid shares in ascending node index (the order of
+    ThresholdDecrypt's share map; a node counts once) straight from the
+    prepared table.  Returns (bools in the order of `shares`, per ciphertext
+    (g96, g48) or None with fewer than threshold + 1 valid shares)."""
+    import numpy as np
+    torch = _torch()
+    outs = [None] * len(ciphertexts)
+    if not shares:
+        return [], outs
+    okh, order, sprep = _verify_grouped(ciphertexts, [(c, s, pk) for c, _, s, pk in shares],
+                                        device)
+    flags = [False] * len(shares)
+    valid = [[] for _ in ciphertexts]   # per ciphertext: (node index, table row)
     for r, i in enumerate(order):
-        out[i] = okh[r] == CHECK_OK
-    return out
+        flags[i] = okh[r] == CHECK_OK
+        if flags[i]:
+            valid[shares[i][0]].append((shares[i][1], r))
+    rows, idx, offs, cts = [], [], [0], []
+    for c, cand in enumerate(valid):
+        seen, pick = set(), []
+        for node, r in sorted(cand):
+            if node not in seen:
+                seen.add(node)
+                pick.append((node, r))
+        if len(pick) < threshold + 1:
+            continue
+        pick = pick[:threshold + 1]
+        rows += [r for _, r in pick]
+        idx += [node for node, _ in pick]
+        offs.append(len(rows))
+        cts.append(c)
+    if cts:
+        dev = "cuda:%d" % device
+        out = decrypt_combine_prepared(
+            sprep, len(shares), torch.from_numpy(np.asarray(rows, np.int32)).to(dev),
+            _u32_tensor(idx, dev), torch.from_numpy(np.asarray(offs, np.int32)).to(dev))
+        for c, res in zip(cts, _combine_results(*out)):
+            outs[c] = res
+    return flags, outs
 
 
 def pairing_check(a, b, c, d):

@@ -428,7 +428,15 @@ int hbrbc_unframe_fused(const hbrbc_ctx *ctx, size_t shard_len, size_t payload_s
  * order-r subgroup are rejected per item, as the crate's deserialisation
  * (`into_affine`) rejects them.
  * hash_g1_g2 (SHA3 + ChaCha-seeded G2 sampling, once per ciphertext) stays
- * with the caller, which passes the G2 point. */
+ * with the caller, which passes the G2 point.
+ *   `PublicKeySet::decrypt`               (threshold_decrypt.rs:232-252, try_output)
+ *       g = sum_i lambda_i share_i, the Lagrange interpolation at 0 of more
+ *       than num_faulty valid shares in G1 (x_i = node index + 1, lambda_i =
+ *       prod_{j != i} x_j / (x_j - x_i) in the scalar field Fr), from the
+ *       shares as hbrbc_g1_prepare left them on the device; the
+ *       hbrbc_lagrange_coeffs .. hbrbc_decrypt_combine entries below.
+ *       xor_with_hash(g, V), which turns g into the plaintext, stays with the
+ *       caller like hash_g1_g2; it hashes the compressed encoding of g. */
 #define HBRBC_G1_BYTES 96
 #define HBRBC_G2_BYTES 192
 #define HBRBC_GT_BYTES 576
@@ -498,6 +506,52 @@ int hbrbc_pairing_check_prepared_pts(const void *a_prepared, const void *keys, s
  * invalid point. */
 int hbrbc_pairing_check(const uint8_t a[96], const uint8_t b[192], const uint8_t c[96],
                         const uint8_t d[192], int *result);
+/* Combining decryption shares: batches of ragged groups.  Group g holds the
+ * entries offsets[g] .. offsets[g + 1] - 1 of the flat per-share arrays
+ * (offsets: groups + 1 entries, a prefix sum; offsets[groups] is the share
+ * count, which each entry reads back from the device -- one 4-byte copy that
+ * waits for the stream -- before it queues its kernels).  Per-group status:
+ * 0 ok, 1 ok and the result is the point at infinity, 2 an invalid input in
+ * the group (invalid table entry, row outside the table, scalar >= r), 3 two
+ * equal indices in the group (the crate's DuplicateEntry).  Results come in
+ * two encodings: out96 + 96 g the uncompressed one (as the inputs), out48 +
+ * 48 g zkcrypto's G1Compressed (x big-endian with 0x80 set in byte 0, 0x20 set
+ * iff y > p - y; infinity = 0xC0 and 47 zero bytes); for statuses 2 and 3
+ * both are zero bytes, and a failed group never affects another.  An empty
+ * group is the empty sum (status 1).  Device memory, async on `stream`. */
+#define HBRBC_G1_COMPRESSED_BYTES 48
+#define HBRBC_FR_BYTES 32
+/* Device workspace bytes of the three entries below. */
+size_t hbrbc_g1_combine_workspace_size(size_t total_shares, size_t groups);
+/* lambda of every share: idx holds the node indices (x = idx + 1, formed in
+ * 64 bits), coeffs_out + 32 j receives lambda_j as 32 big-endian bytes
+ * (canonical, < r; zero bytes where the index repeats), status_out[g] = 0 or
+ * 3.  Needs no workspace. */
+int hbrbc_lagrange_coeffs(const uint32_t *idx, const uint32_t *offsets, size_t groups,
+                          uint8_t *coeffs_out, uint8_t *status_out, void *stream);
+/* Per group sum_j scalars[j] * T[rows[j]] over a table T of hbrbc_g1_prepare:
+ * rows int32 per share, scalars 32 big-endian bytes per share.
+ * `prepared_count` is the count the table was prepared with (the position of
+ * its status bytes depends on it: pass that count, whatever the rows use).
+ * A zero scalar and a table entry at infinity contribute the identity. */
+int hbrbc_g1_lincomb_prepared(const void *a_prepared, size_t prepared_count, const int32_t *rows,
+                              const uint8_t *scalars, const uint32_t *offsets, size_t groups,
+                              uint8_t *out96, uint8_t *out48, uint8_t *status_out,
+                              void *workspace, void *stream);
+/* `PublicKeySet::decrypt` up to g: the two above in sequence, share j of a
+ * group being T[rows[j]] from node idx[j]. */
+int hbrbc_decrypt_combine_prepared(const void *a_prepared, size_t prepared_count,
+                                   const int32_t *rows, const uint32_t *idx,
+                                   const uint32_t *offsets, size_t groups, uint8_t *out96,
+                                   uint8_t *out48, uint8_t *status_out, void *workspace,
+                                   void *stream);
+/* Per-call shim on host memory (one group of n shares, 96 bytes each, from
+ * nodes idx[0..n); synchronous, current device): decodes and checks the
+ * shares and combines them.  HBRBC_E_INVALID_ARG for an invalid share or a
+ * repeated index (statuses 2 and 3); a result at infinity is returned in its
+ * encodings. */
+int hbrbc_decrypt_combine(const uint8_t *shares, const uint32_t *idx, size_t n, uint8_t out96[96],
+                          uint8_t out48[48]);
 
 /* ---- the Broadcast state machine, batched --------------- */
 /* Many instances x nodes of `Broadcast` (broadcast.rs:228-558) in synchronous
