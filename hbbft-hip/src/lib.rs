@@ -190,3 +190,24 @@ pub fn decrypt_combine(shares: &[[u8; 96]], indices: &[u32]) -> Option<([u8; 96]
         _ => fail_loudly(st), // a device error panics
     }
 }
+
+/// `combine_signatures` of `ThresholdSign` (threshold_sign.rs:249-270): the
+/// Lagrange interpolation at 0 of `shares` in G2 on the GPU, share i coming
+/// from node `indices[i]`.  Returns the signature in the pairing crate's
+/// uncompressed and compressed encodings and its parity (the coin of
+/// `BinaryAgreement`: the XOR of all bits of the uncompressed encoding), or
+/// `None` for an invalid share or a repeated index (the crate's
+/// `DuplicateEntry`).
+pub fn sig_combine(shares: &[[u8; 192]], indices: &[u32]) -> Option<([u8; 192], [u8; 96], bool)> {
+    assert_eq!(shares.len(), indices.len());
+    let (mut s192, mut s96, mut parity) = ([0u8; 192], [0u8; 96], 0u8);
+    let st = unsafe {
+        ffi::hbrbc_sig_combine(shares.as_ptr() as *const u8, indices.as_ptr(), shares.len(),
+                               s192.as_mut_ptr(), s96.as_mut_ptr(), &mut parity)
+    };
+    match st {
+        0 => Some((s192, s96, parity != 0)),
+        100 => None, // HBRBC_E_INVALID_ARG: the group's status was 2 or 3
+        _ => fail_loudly(st), // a device error panics
+    }
+}

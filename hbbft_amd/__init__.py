@@ -155,6 +155,17 @@ def lib():
                                                           _P]),
         "hbrbc_decrypt_combine": (ctypes.c_int, [ctypes.c_char_p, _P, _S, ctypes.c_char_p,
                                                  ctypes.c_char_p]),
+        "hbrbc_g2_points_size": (_S, [_S]),
+        "hbrbc_g2_points_prepare": (ctypes.c_int, [_P, _S, _P, _P]),
+        "hbrbc_sig_check_prepared": (ctypes.c_int, [_P, _S, _P, _S, _P, _P, _S, _P, _S, _P, _P,
+                                                    _P]),
+        "hbrbc_g2_combine_workspace_size": (_S, [_S, _S]),
+        "hbrbc_g2_lincomb_prepared": (ctypes.c_int, [_P, _S, _P, _P, _P, _S, _P, _P, _P, _P, _P,
+                                                     _P]),
+        "hbrbc_sig_combine_prepared": (ctypes.c_int, [_P, _S, _P, _P, _P, _S, _P, _P, _P, _P, _P,
+                                                      _P]),
+        "hbrbc_sig_combine": (ctypes.c_int, [ctypes.c_char_p, _P, _S, ctypes.c_char_p,
+                                             ctypes.c_char_p, ctypes.c_char_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -2540,6 +2540,171 @@ int hbrbc_decrypt_combine(const uint8_t *shares, const uint32_t *idx, size_t n, 
     return HBRBC_OK;
 }
 
+// ---- threshold signatures (pairing.hip): ThresholdSign, the coin ----------
+size_t hbrbc_g2_points_size(size_t points) {
+    return round_up(g2_point_table_words(points) * 4, 256) + round_up(points, 256);
+}
+
+// the status bytes of a g2_points table sit behind the coordinates of the
+// count it was prepared with
+static const uint8_t *g2_points_status(const void *table, size_t count) {
+    return static_cast<const uint8_t *>(table) + round_up(g2_point_table_words(count) * 4, 256);
+}
+
+int hbrbc_g2_points_prepare(const uint8_t *g2, size_t count, void *table, void *stream) {
+    if (count == 0) return HBRBC_OK;
+    if (!g2 || !table) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_g2_points(g2, count, static_cast<uint32_t *>(table),
+                            const_cast<uint8_t *>(g2_points_status(table, count)),
+                            static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
+int hbrbc_sig_check_prepared(const void *sig_table, size_t sig_count, const void *keys,
+                             size_t key_points, const uint32_t *idx_key, const void *prepared,
+                             size_t points, const uint32_t *idx_h, size_t count, uint8_t *ok_out,
+                             void *workspace, void *stream) {
+    if (count == 0) return HBRBC_OK;
+    if (!sig_table || !keys || !idx_key || !prepared || !idx_h || !ok_out || !workspace)
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (points == 0) return fail(HBRBC_E_INVALID_ARG, "no prepared points");
+    if (key_points == 0) return fail(HBRBC_E_INVALID_ARG, "no prepared keys");
+    if (sig_count == 0) return fail(HBRBC_E_INVALID_ARG, "no signature shares");
+    if (int rc = have_device()) return rc;
+    const uint32_t *kw = static_cast<const uint32_t *>(keys);
+    const uint8_t *kst =
+        static_cast<const uint8_t *>(keys) + round_up(g1_key_words(key_points) * 4, 256);
+    const uint32_t *prep = static_cast<const uint32_t *>(prepared);
+    const uint8_t *pst =
+        static_cast<const uint8_t *>(prepared) + round_up(pairing_prepared_words(points) * 4, 256);
+    uint32_t *ws = static_cast<uint32_t *>(workspace);
+    uint8_t *st = static_cast<uint8_t *>(workspace) + round_up(count * 576, 256);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HB_HIP(launch_pairing_miller_sig(static_cast<const uint32_t *>(sig_table),
+                                     g2_points_status(sig_table, sig_count), sig_count, kw, kst,
+                                     idx_key, key_points, prep, pst, idx_h, points, count, ws, st,
+                                     s));
+    HB_HIP(launch_pairing_final(ws, count, count, 1, st, nullptr, ok_out, s));
+    return HBRBC_OK;
+}
+
+// workspace of the G2 combine: as CombineWs, the points over Fp2
+static CombineWs g2_combine_ws(void *workspace, size_t total) {
+    uint8_t *p = static_cast<uint8_t *>(workspace);
+    CombineWs w;
+    w.pts = reinterpret_cast<uint32_t *>(p);
+    p += round_up(g2_point_words(total) * 4, 256);
+    w.pst = p;
+    p += round_up(total, 256);
+    w.coeffs = p;
+    p += round_up(total * 32, 256);
+    w.lst = p;
+    return w;
+}
+
+size_t hbrbc_g2_combine_workspace_size(size_t total_shares, size_t groups) {
+    return round_up(g2_point_words(total_shares) * 4, 256) + round_up(total_shares, 256) +
+           round_up(total_shares * 32, 256) + round_up(groups, 256);
+}
+
+static int g2_lincomb_run(const void *table, size_t table_count, const int32_t *rows,
+                          const uint8_t *scalars, const uint32_t *offsets, size_t groups,
+                          size_t total, const uint8_t *lst, uint8_t *out192, uint8_t *out96,
+                          uint8_t *parity_out, uint8_t *status_out, const CombineWs &w,
+                          hipStream_t s) {
+    HB_HIP(launch_g2_scalar_mul(static_cast<const uint32_t *>(table),
+                                g2_points_status(table, table_count), table_count, rows, scalars,
+                                total, w.pts, w.pst, s));
+    HB_HIP(launch_g2_reduce_encode(w.pts, w.pst, offsets, groups, total, lst, out192, out96,
+                                   parity_out, status_out, s));
+    return HBRBC_OK;
+}
+
+int hbrbc_g2_lincomb_prepared(const void *sig_table, size_t sig_count, const int32_t *rows,
+                              const uint8_t *scalars, const uint32_t *offsets, size_t groups,
+                              uint8_t *out192, uint8_t *out96, uint8_t *parity_out,
+                              uint8_t *status_out, void *workspace, void *stream) {
+    if (groups == 0) return HBRBC_OK;
+    if (!sig_table || !offsets || !out192 || !out96 || !parity_out || !status_out || !workspace)
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    size_t total = 0;
+    if (int rc = combine_total(offsets, groups, s, &total)) return rc;
+    if (total && (!rows || !scalars)) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    return g2_lincomb_run(sig_table, sig_count, rows, scalars, offsets, groups, total, nullptr,
+                          out192, out96, parity_out, status_out, g2_combine_ws(workspace, total),
+                          s);
+}
+
+int hbrbc_sig_combine_prepared(const void *sig_table, size_t sig_count, const int32_t *rows,
+                               const uint32_t *idx, const uint32_t *offsets, size_t groups,
+                               uint8_t *out192, uint8_t *out96, uint8_t *parity_out,
+                               uint8_t *status_out, void *workspace, void *stream) {
+    if (groups == 0) return HBRBC_OK;
+    if (!sig_table || !offsets || !out192 || !out96 || !parity_out || !status_out || !workspace)
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    size_t total = 0;
+    if (int rc = combine_total(offsets, groups, s, &total)) return rc;
+    if (total && (!rows || !idx)) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    const CombineWs w = g2_combine_ws(workspace, total);
+    HB_HIP(hipMemsetAsync(w.lst, 0, groups, s));
+    HB_HIP(launch_lagrange(idx, offsets, groups, total, w.coeffs, w.lst, s));
+    return g2_lincomb_run(sig_table, sig_count, rows, w.coeffs, offsets, groups, total, w.lst,
+                          out192, out96, parity_out, status_out, w, s);
+}
+
+int hbrbc_sig_combine(const uint8_t *shares, const uint32_t *idx, size_t n, uint8_t out192[192],
+                      uint8_t out96[96], uint8_t *parity) {
+    if (!out192 || !out96 || !parity || (n && (!shares || !idx)))
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    // device block: shares | idx | rows | offsets | out192, out96, parity,
+    // status | point table | workspace
+    const size_t o_idx = round_up(n * 192, 256), o_rows = o_idx + round_up(n * 4, 256);
+    const size_t o_off = o_rows + round_up(n * 4, 256), o_out = o_off + 256;
+    const size_t o_tab = o_out + 512, o_ws = o_tab + hbrbc_g2_points_size(n);
+    const size_t bytes = o_ws + hbrbc_g2_combine_workspace_size(n, 1);
+    uint8_t *dev = nullptr;
+    HB_HIP(hipMalloc(&dev, bytes));
+    std::vector<uint8_t> host(o_out, 0);
+    if (n) {
+        memcpy(host.data(), shares, n * 192);
+        memcpy(host.data() + o_idx, idx, n * 4);
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const int32_t r = (int32_t)i;
+        memcpy(host.data() + o_rows + 4 * i, &r, 4);
+    }
+    const uint32_t offs[2] = {0, (uint32_t)n};
+    memcpy(host.data() + o_off, offs, sizeof offs);
+    uint8_t out[512] = {0};
+    int rc = HBRBC_OK;
+    hipError_t e = hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = hbrbc_g2_points_prepare(dev, n, dev + o_tab, nullptr);
+        if (rc == HBRBC_OK)
+            rc = hbrbc_sig_combine_prepared(
+                dev + o_tab, n, reinterpret_cast<const int32_t *>(dev + o_rows),
+                reinterpret_cast<const uint32_t *>(dev + o_idx),
+                reinterpret_cast<const uint32_t *>(dev + o_off), 1, dev + o_out, dev + o_out + 192,
+                dev + o_out + 288, dev + o_out + 289, dev + o_ws, nullptr);
+        if (rc == HBRBC_OK) e = hipMemcpy(out, dev + o_out, 290, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(dev);
+    if (e != hipSuccess) return fail(HBRBC_E_DEVICE, "signature combine: %s", hipGetErrorString(e));
+    if (rc != HBRBC_OK) return rc;
+    if (out[289] == 3) return fail(HBRBC_E_INVALID_ARG, "duplicate share index");
+    if (out[289] == 2) return fail(HBRBC_E_INVALID_ARG, "invalid curve point");
+    memcpy(out192, out, 192);
+    memcpy(out96, out + 192, 96);
+    *parity = out[288];
+    return HBRBC_OK;
+}
+
 // ---- f2: the Broadcast state machine, batched (sim.hip) -------------------
 size_t hbrbc_sm_state_bytes(size_t n, size_t roots) { return sm_state_bytes(n, roots); }
 

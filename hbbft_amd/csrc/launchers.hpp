@@ -281,6 +281,26 @@ hipError_t launch_g1_scalar_mul(const uint32_t *tab, const uint8_t *tst, size_t 
 hipError_t launch_g1_reduce_encode(const uint32_t *ws, const uint8_t *pst, const uint32_t *offsets,
                                    size_t groups, size_t total, const uint8_t *lst, uint8_t *out96,
                                    uint8_t *out48, uint8_t *status, hipStream_t s);
+// threshold signatures (pairing.hip): decoded G2 points (a table of
+// g2_point_table_words(points) words), the share check e(K, P) == e(G1::one(),
+// S) with S from that table, [k] Q per share into a limb-major workspace of
+// g2_point_words(total) words, per-group sum, encodings and parity
+size_t g2_point_table_words(size_t points);
+size_t g2_point_words(size_t shares);
+hipError_t launch_g2_points(const uint8_t *g2, size_t count, uint32_t *tab, uint8_t *gst,
+                            hipStream_t s);
+hipError_t launch_pairing_miller_sig(const uint32_t *stab, const uint8_t *sst, size_t nsig,
+                                     const uint32_t *keys, const uint8_t *kst, const uint32_t *ic,
+                                     size_t nkeys, const uint32_t *prep, const uint8_t *pst,
+                                     const uint32_t *ih, size_t points, size_t count, uint32_t *ws,
+                                     uint8_t *status, hipStream_t s);
+hipError_t launch_g2_scalar_mul(const uint32_t *tab, const uint8_t *tst, size_t nprep,
+                                const int32_t *rows, const uint8_t *scalars, size_t total,
+                                uint32_t *ws, uint8_t *pst, hipStream_t s);
+hipError_t launch_g2_reduce_encode(const uint32_t *ws, const uint8_t *pst, const uint32_t *offsets,
+                                   size_t groups, size_t total, const uint8_t *lst,
+                                   uint8_t *out192, uint8_t *out96, uint8_t *parity,
+                                   uint8_t *status, hipStream_t s);
 
 hipError_t configure_kernels();
 

@@ -1556,7 +1556,10 @@ DEV void fr_shl1(Fr &k) {
     k.l[0] <<= 1;
 }
 
-#if HB_G1_GLV
+#ifndef HB_G2_GLV
+#define HB_G2_GLV 1   // the same split on G2 (g2_scalar_mul_kernel below)
+#endif
+#if HB_G1_GLV || HB_G2_GLV
 // k = k1 + k2 x^2, k < r: bit-serial long division by the 128-bit x^2 (a few
 // thousand integer operations against a million in the curve arithmetic)
 DEV void glv_split(Fr k, uint64_t &k1hi, uint64_t &k1lo, uint64_t &k2hi, uint64_t &k2lo) {
@@ -1848,6 +1851,351 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
     store_f12(ws, count, i, f);
 }
 
+// ------------------------------------------------- threshold signatures
+// ThresholdSign, the common coin of BinaryAgreement (threshold_sign.rs): every
+// received share is checked with `pk_i.verify_g2(share, H)` (:216-225),
+//
+//     e(pk_i, H) == e(G1::one(), share_i),     H = hash_g2(doc),
+//
+// and more than num_faulty valid shares are combined by the Lagrange
+// interpolation at 0 in G2 (`combine_signatures`, :249-270), the result being
+// checked once more against the master public key.  The G2 point on the right
+// differs per share, so it cannot come from the prepared-lines table: the
+// shares are decoded and order-checked once into a table of affine points
+// (g2_points_kernel, the G2 twin of g1_prepare_kernel), from which the check
+// walks its twist chain and the combine takes its operands.
+constexpr int kG2PtWords = 4 * NL;   // x.c0, x.c1, y.c0, y.c1 (Montgomery)
+
+DEV void load_g2_pt(const uint32_t *src, Fp2 &x, Fp2 &y) {
+    Fp *v[4] = {&x.c0, &x.c1, &y.c0, &y.c1};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int w = 0; w < NL; w += 4) {
+            const uint4 q = *reinterpret_cast<const uint4 *>(src + e * NL + w);
+            v[e]->l[w] = q.x;
+            v[e]->l[w + 1] = q.y;
+            v[e]->l[w + 2] = q.z;
+            v[e]->l[w + 3] = q.w;
+        }
+}
+
+// One lane per G2 point: decoded and checked (canonical coordinates, on the
+// twist, order r), stored as Montgomery affine coordinates (zeros unless the
+// point is valid and finite), status at gst[q] (0 ok, 1 infinity, 2 invalid).
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void g2_points_kernel(
+    const uint8_t *__restrict__ g2, size_t count, uint32_t *__restrict__ tab,
+    uint8_t *__restrict__ gst) {
+    const size_t q = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (q >= count) return;
+    Fp2 x, y;
+    const int st = decode_g2(g2 + q * 192, x, y);
+    if (st != PT_OK) {
+        fp2_zero(x);
+        fp2_zero(y);
+    }
+    const Fp *v[4] = {&x.c0, &x.c1, &y.c0, &y.c1};
+    uint32_t *dst = tab + q * kG2PtWords;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int w = 0; w < NL; w += 4)
+            *reinterpret_cast<uint4 *>(dst + e * NL + w) =
+                make_uint4(v[e]->l[w], v[e]->l[w + 1], v[e]->l[w + 2], v[e]->l[w + 3]);
+    gst[q] = (uint8_t)st;
+}
+
+// One lane per check e(K[ic[i]], P[ih[i]]) == e(G1::one(), S[i]), evaluated as
+// f_{K,P} * f_{-G1::one(),S}.  Leg 1 is the c leg of miller_prepared_kernel:
+// the key from a g1_prepare table, the lines of P from a g2_prepare table
+// (lanes of a wave checking one document read the same lines).  Leg 2 walks
+// T from S[i], entry i of a g2_points table of `nsig` points, and applies its
+// lines at the constant -G1::one().  Both legs share one squaring of f per
+// bit.  An invalid point, an index past its table or i >= nsig gives status 2;
+// an infinity drops its leg.
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void miller_sig_kernel(
+    const uint32_t *__restrict__ stab, const uint8_t *__restrict__ sst, size_t nsig,
+    const uint32_t *__restrict__ keys, const uint8_t *__restrict__ kst,
+    const uint32_t *__restrict__ ic, size_t nkeys, const uint32_t *__restrict__ prep,
+    const uint8_t *__restrict__ pst, const uint32_t *__restrict__ ih, size_t points, size_t count,
+    uint32_t *__restrict__ ws, uint8_t *__restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (i >= count) return;
+    // an index past its table is an invalid input, never an out-of-bounds read
+    const uint32_t qk = ic[i];
+    uint32_t qh = ih[i];
+    const int sk = qk < nkeys ? kst[qk] : PT_BAD;
+    const int sh = qh < points ? pst[qh] : PT_BAD;
+    const int ss = i < nsig ? sst[i] : PT_BAD;
+    if (qh >= points) qh = 0;
+    Fp xk, yk;
+    if (sk == PT_OK) {
+        load_g1_key(keys + (size_t)qk * kG1KeyWords, xk, yk);
+    } else {
+        fp_zero(xk);
+        fp_zero(yk);
+    }
+    const bool bad = sk == PT_BAD || sh == PT_BAD || ss == PT_BAD;
+    const bool on1 = !bad && sk == PT_OK && sh == PT_OK;
+    const bool on2 = !bad && ss == PT_OK;
+    Fp12 f;
+    fp12_one(f);
+    if (on1 || on2) {
+        Fp gx, gy;
+        fp_set(gx, kG1GenX);
+        fp_set(gy, kG1GenNegY);   // e(-G1::one(), S) = e(G1::one(), S)^-1
+        Fp2 xs, ys;
+        G2Proj T;
+        if (on2) {
+            load_g2_pt(stab + i * kG2PtWords, xs, ys);
+        } else {
+            fp2_zero(xs);
+            fp2_zero(ys);
+        }
+        T.x = xs;
+        T.y = ys;
+        fp_set(T.z.c0, kOne);
+        fp_zero(T.z.c1);
+        const uint32_t *p1 = prep + (size_t)qh * kLines * kLineWords;
+        for (int b = 62; b >= 0; --b) {
+            if (HB_MILLER_INL) miller_sqr(f); else fp12_sqr(f, f);
+            if (on1) HB_APPLY_PREPARED(f, p1, xk, yk);
+            if (on2) miller_dbl(T, f, gx, gy);
+            p1 += kLineWords;
+            if ((kXAbs >> b) & 1u) {
+                if (on1) HB_APPLY_PREPARED(f, p1, xk, yk);
+                if (on2) miller_add(T, f, xs, ys, gx, gy);
+                p1 += kLineWords;
+            }
+        }
+        fp12_conj(f, f);
+    }
+    status[i] = bad ? PT_BAD : PT_OK;
+    store_f12(ws, count, i, f);
+}
+
+// Projective G2 points between the kernels: limb-major like store_pt
+// (X, Y, Z over Fp2: kPt2Words words).
+constexpr int kPt2Words = 6 * NL;
+
+DEV void store_pt(uint32_t *ws, size_t n, size_t j, const PtProj<Fp2> &p) {
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(&p);
+#pragma unroll 4
+    for (int w = 0; w < kPt2Words; ++w) ws[(size_t)w * n + j] = src[w];
+}
+
+DEV void load_pt(PtProj<Fp2> &p, const uint32_t *ws, size_t n, size_t j) {
+    uint32_t *dst = reinterpret_cast<uint32_t *>(&p);
+#pragma unroll 4
+    for (int w = 0; w < kPt2Words; ++w) dst[w] = ws[(size_t)w * n + j];
+}
+
+DEV void pt_identity(PtProj<Fp2> &p) {
+    fp2_zero(p.x);
+    fe_one(p.y);
+    fp2_zero(p.z);
+}
+
+// p <- p + q on the twist, both projective: pt_add_proj above over Fp2 (the
+// same algorithm 7 with a = 0 and 3b = 12 (u + 1)).  E'(Fp2) has even order,
+// so the formulas are not complete on all of it; they are on the order-r
+// subgroup (odd order: no point of order 2, the only exception), and every
+// operand here is a checked G2 point or a sum of such.  An overload, not a
+// template: the G1 kernels keep the code they were measured with.
+NOINL void pt_add_proj(PtProj<Fp2> &p, const PtProj<Fp2> &q) {
+    Fp2 t0, t1, t2, t3, t4, x3, y3, z3;
+    fe_mul(t0, p.x, q.x);
+    fe_mul(t1, p.y, q.y);
+    fe_mul(t2, p.z, q.z);
+    fe_add(t3, p.x, p.y);
+    fe_add(t4, q.x, q.y);
+    fe_mul(t3, t3, t4);
+    fe_add(t4, t0, t1);
+    fe_sub(t3, t3, t4);             // X1 Y2 + X2 Y1
+    fe_add(t4, p.y, p.z);
+    fe_add(x3, q.y, q.z);
+    fe_mul(t4, t4, x3);
+    fe_add(x3, t1, t2);
+    fe_sub(t4, t4, x3);             // Y1 Z2 + Y2 Z1
+    fe_add(x3, p.x, p.z);
+    fe_add(y3, q.x, q.z);
+    fe_mul(x3, x3, y3);
+    fe_add(y3, t0, t2);
+    fe_sub(y3, x3, y3);             // X1 Z2 + X2 Z1
+    fe_add(x3, t0, t0);
+    fe_add(t0, x3, t0);
+    fe_mul_b3(t2, t2);
+    fe_add(z3, t1, t2);
+    fe_sub(t1, t1, t2);
+    fe_mul_b3(y3, y3);
+    fe_mul(x3, t4, y3);
+    fe_mul(t2, t3, t1);
+    fe_sub(x3, t2, x3);
+    fe_mul(y3, y3, t0);
+    fe_mul(t1, t1, z3);
+    fe_add(y3, t1, y3);
+    fe_mul(t0, t0, t3);
+    fe_mul(z3, z3, t4);
+    fe_add(p.z, z3, t0);
+    p.x = x3;
+    p.y = y3;
+}
+
+// HB_G2_GLV: the G2 scalar multiplication through the endomorphism (1) or
+// plain double-and-add over 255 bits (0) (A/B).  psi(Q) = [x] Q
+// on G2 (g2_in_subgroup above), so psi^2(Q) = (gamma x, -y) = [x^2] Q with
+// gamma in Fp (bls_consts.hpp) -- no sign flip, unlike phi on G1, and the
+// same shape of operand: with k = k1 + k2 x^2 (glv_split, unchanged)
+//     [k] Q = [k1] Q + [k2] psi^2(Q),
+// two 128-bit halves on one doubling chain, one selected-operand addition per
+// bit pair as in g1_scalar_mul_kernel.  HB_G2_GLV = 1 is the default (set
+// beside HB_G1_GLV), -DHB_G2_GLV=0 builds the plain form.
+
+// Kernel: one lane per share, [k_j] Q_j.  Q_j = row rows[j] of a g2_points
+// table of `nprep` points, k_j = 32 big-endian bytes.  k = 0 and a table entry
+// at infinity give the identity; k >= r, an invalid table entry and a row
+// outside the table give pst = 2.
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void g2_scalar_mul_kernel(
+    const uint32_t *__restrict__ tab, const uint8_t *__restrict__ tst, size_t nprep,
+    const int32_t *__restrict__ rows, const uint8_t *__restrict__ scalars, size_t total,
+    uint32_t *__restrict__ ws, uint8_t *__restrict__ pst) {
+    const size_t j = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (j >= total) return;
+    const int32_t row = rows[j];
+    // a row past the table is an invalid input, never an out-of-bounds read
+    int st = (row >= 0 && (size_t)row < nprep) ? tst[row] : PT_BAD;
+    Fr k;
+    fr_load_be32(k, scalars + 32 * j);
+    if (!fr_is_canonical(k)) st = PT_BAD;
+    PtProj<Fp2> acc;
+    pt_identity(acc);
+    if (st == PT_OK) {
+        Fp2 x, y;
+        load_g2_pt(tab + (size_t)row * kG2PtWords, x, y);
+#if HB_G2_GLV
+        uint64_t k1hi, k1lo, k2hi, k2lo;
+        glv_split(k, k1hi, k1lo, k2hi, k2lo);
+        PtProj<Fp2> pp, qq, tt;   // Q, psi^2(Q) = (gamma x, -y), their sum
+        Fp gamma;
+        pp.x = x;
+        pp.y = y;
+        fe_one(pp.z);
+        fp_set(gamma, kGammaG2);
+        fp2_mul_fp(qq.x, x, gamma);
+        fp2_neg(qq.y, y);
+        qq.z = pp.z;
+        tt = pp;
+        pt_add_proj(tt, qq);
+        const uint32_t *wp = reinterpret_cast<const uint32_t *>(&pp);
+        const uint32_t *wq = reinterpret_cast<const uint32_t *>(&qq);
+        const uint32_t *wt = reinterpret_cast<const uint32_t *>(&tt);
+        for (int b = 127; b >= 0; --b) {
+            pt_dbl(acc);
+            const unsigned sel = (unsigned)(k1hi >> 63) | ((unsigned)(k2hi >> 63) << 1);
+            k1hi = (k1hi << 1) | (k1lo >> 63);
+            k1lo <<= 1;
+            k2hi = (k2hi << 1) | (k2lo >> 63);
+            k2lo <<= 1;
+            if (sel) {
+                PtProj<Fp2> op;
+                uint32_t *wo = reinterpret_cast<uint32_t *>(&op);
+#pragma unroll
+                for (int w = 0; w < kPt2Words; ++w)
+                    wo[w] = sel == 1 ? wp[w] : (sel == 2 ? wq[w] : wt[w]);
+                pt_add_proj(acc, op);
+            }
+        }
+#else
+        fr_shl1(k);   // bit 254 to the top, then one bit per step
+        for (int b = 254; b >= 0; --b) {
+            pt_dbl(acc);
+            if (k.l[NR - 1] >> 31) pt_add_affine(acc, x, y);
+            fr_shl1(k);
+        }
+#endif
+    }
+    pst[j] = (uint8_t)(st == PT_BAD ? PT_BAD : PT_OK);
+    store_pt(ws, total, j, acc);
+}
+
+// Kernel: one lane per group.  Sums the group's projective points, converts
+// to affine with one Fp2 inversion and writes the uncompressed encoding (192
+// bytes, x.c1 || x.c0 || y.c1 || y.c0), the compressed one (96 bytes: x.c1 ||
+// x.c0 with 0x80 set, 0x20 set iff y is the larger of y and -y, c1 compared
+// first and c0 only when the c1 are equal; infinity = 0xC0 and zeros) --
+// zkcrypto's G2Uncompressed / G2Compressed -- and the parity byte: the XOR of
+// all bits of the uncompressed encoding (threshold_crypto's
+// Signature::parity(), the coin).  status as g1_reduce_encode_kernel; for 2
+// and 3 all three outputs are zero bytes.  An empty group is status 1.
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void g2_reduce_encode_kernel(
+    const uint32_t *__restrict__ ws, const uint8_t *__restrict__ pst,
+    const uint32_t *__restrict__ offsets, size_t groups, size_t total,
+    const uint8_t *__restrict__ lst, uint8_t *__restrict__ out192, uint8_t *__restrict__ out96,
+    uint8_t *__restrict__ parity, uint8_t *__restrict__ status) {
+    const size_t g = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (g >= groups) return;
+    size_t b, e;
+    group_range(offsets, g, total, b, e);
+    int st = (lst && lst[g] == CB_DUP) ? CB_DUP : CB_OK;
+    if (st == CB_OK)
+        for (size_t k = b; k < e; ++k)
+            if (pst[k] == PT_BAD) st = CB_BAD;
+    uint8_t *o192 = out192 + 192 * g, *o96 = out96 + 96 * g;
+    for (int i = 0; i < 192; ++i) o192[i] = 0;
+    for (int i = 0; i < 96; ++i) o96[i] = 0;
+    uint8_t par = 0;
+    if (st == CB_OK) {
+        PtProj<Fp2> acc, q;
+        pt_identity(acc);
+        for (size_t k = b; k < e; ++k) {
+            load_pt(q, ws, total, k);
+            pt_add_proj(acc, q);
+        }
+        if (fp2_is_zero(acc.z)) {
+            st = CB_INF;
+            o192[0] = 0x40;
+            o96[0] = 0xC0;
+            par = 1;
+        } else {
+            Fp2 zi, x, y;
+            fp2_inv(zi, acc.z);
+            fp2_mul(x, acc.x, zi);
+            fp2_mul(y, acc.y, zi);
+            from_mont(x.c0, x.c0);
+            from_mont(x.c1, x.c1);
+            from_mont(y.c0, y.c0);
+            from_mont(y.c1, y.c1);
+            // -y = (p - c0, p - c1), a zero coefficient staying zero; y against
+            // -y by c1, most significant limb first, then by c0
+            int cmp = 0;   // sign of y - (-y)
+#pragma unroll
+            for (int c = 1; c >= 0; --c) {
+                const Fp &yc = c ? y.c1 : y.c0;
+                Fp nc;
+                uint32_t br = 0;
+#pragma unroll
+                for (int i = 0; i < NL; ++i) nc.l[i] = subb(kP[i], yc.l[i], br, &br);
+                if (fp_is_zero(yc)) nc = yc;
+#pragma unroll
+                for (int i = NL - 1; i >= 0; --i)
+                    if (cmp == 0 && yc.l[i] != nc.l[i]) cmp = yc.l[i] > nc.l[i] ? 1 : -1;
+            }
+            store_be48_raw(o192, x.c1, 0);
+            store_be48_raw(o192 + 48, x.c0, 0);
+            store_be48_raw(o192 + 96, y.c1, 0);
+            store_be48_raw(o192 + 144, y.c0, 0);
+            store_be48_raw(o96, x.c1, (uint8_t)(0x80 | (cmp > 0 ? 0x20 : 0)));
+            store_be48_raw(o96 + 48, x.c0, 0);
+            uint32_t acc32 = 0;
+#pragma unroll
+            for (int i = 0; i < NL; ++i) acc32 ^= x.c0.l[i] ^ x.c1.l[i] ^ y.c0.l[i] ^ y.c1.l[i];
+            par = (uint8_t)(__popc(acc32) & 1);
+        }
+    }
+    parity[g] = par;
+    status[g] = (uint8_t)st;
+}
+
 // The crate's final exponentiation (Bls12::final_exponentiation): easy part
 // f^((p^6 - 1)(p^2 + 1)), then the hard-part chain.
 DEV void final_exp(Fp12 &out, const Fp12 &f) {
@@ -2032,6 +2380,51 @@ hipError_t launch_g1_reduce_encode(const uint32_t *ws, const uint8_t *pst, const
     const unsigned blocks = (unsigned)((groups + kPairBlock - 1) / kPairBlock);
     hipLaunchKernelGGL(g1_reduce_encode_kernel, dim3(blocks), dim3(kPairBlock), 0, s, ws, pst,
                        offsets, groups, total, lst, out96, out48, status);
+    return hipGetLastError();
+}
+
+size_t g2_point_table_words(size_t points) { return points * (size_t)kG2PtWords; }
+size_t g2_point_words(size_t shares) { return shares * (size_t)kPt2Words; }
+
+hipError_t launch_g2_points(const uint8_t *g2, size_t count, uint32_t *tab, uint8_t *gst,
+                            hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g2_points_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g2, count, tab, gst);
+    return hipGetLastError();
+}
+
+hipError_t launch_pairing_miller_sig(const uint32_t *stab, const uint8_t *sst, size_t nsig,
+                                     const uint32_t *keys, const uint8_t *kst, const uint32_t *ic,
+                                     size_t nkeys, const uint32_t *prep, const uint8_t *pst,
+                                     const uint32_t *ih, size_t points, size_t count, uint32_t *ws,
+                                     uint8_t *status, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    if (points == 0 || nkeys == 0) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(miller_sig_kernel, dim3(blocks), dim3(kPairBlock), 0, s, stab, sst, nsig,
+                       keys, kst, ic, nkeys, prep, pst, ih, points, count, ws, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_g2_scalar_mul(const uint32_t *tab, const uint8_t *tst, size_t nprep,
+                                const int32_t *rows, const uint8_t *scalars, size_t total,
+                                uint32_t *ws, uint8_t *pst, hipStream_t s) {
+    if (total == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((total + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g2_scalar_mul_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab, tst, nprep,
+                       rows, scalars, total, ws, pst);
+    return hipGetLastError();
+}
+
+hipError_t launch_g2_reduce_encode(const uint32_t *ws, const uint8_t *pst, const uint32_t *offsets,
+                                   size_t groups, size_t total, const uint8_t *lst,
+                                   uint8_t *out192, uint8_t *out96, uint8_t *parity,
+                                   uint8_t *status, hipStream_t s) {
+    if (groups == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((groups + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g2_reduce_encode_kernel, dim3(blocks), dim3(kPairBlock), 0, s, ws, pst,
+                       offsets, groups, total, lst, out192, out96, parity, status);
     return hipGetLastError();
 }
 

@@ -24,6 +24,18 @@ prepared table the checks read, so the verified shares never leave the device;
 hash_g1_g2) stays with the caller; it hashes the compressed encoding of g,
 which comes back beside the uncompressed one.
 
+`ThresholdSign` (threshold_sign.rs), the common coin of `BinaryAgreement`, is
+the third consumer: every received signature share goes through
+`pk_i.verify_g2(share, hash)` (lines 216-225),
+
+    PublicKeyShare::verify_g2               e(pk_i, H) == e(G1::one(), share_i)
+
+and `combine_and_verify_sig` (lines 249-270) interpolates t + 1 valid shares
+at 0 in G2 and checks the result against the master public key; the coin is
+the signature's parity.  `sig_check_prepared` and `sig_combine_prepared` are
+the two steps on device tables, `threshold_sign_grouped` the whole for many
+coins.  H = hash_g2(doc) stays with the caller and arrives as a G2 point.
+
 Points are the crate's uncompressed encodings (G1: 96 bytes, G2: 192 bytes,
 big-endian; see include/hbrbc.h).  There is no CPU fallback: without the
 library or a GPU the calls raise `HbrbcUnavailable`.
@@ -44,6 +56,7 @@ G1_ONE = bytes.fromhex(
 CHECK_OK, CHECK_FAIL, CHECK_INVALID = 1, 0, 2
 
 G1_COMPRESSED_BYTES = 48
+G2_COMPRESSED_BYTES = 96
 FR_BYTES = 32
 # per-group status of the combine entries
 COMBINE_OK, COMBINE_INFINITY, COMBINE_INVALID, COMBINE_DUPLICATE = 0, 1, 2, 3
@@ -452,6 +465,298 @@ def decrypt_shares_grouped(ciphertexts, shares, threshold, device=0):
             _u32_tensor(idx, dev), torch.from_numpy(np.asarray(offs, np.int32)).to(dev))
         for c, res in zip(cts, _combine_results(*out)):
             outs[c] = res
+    return flags, outs
+
+
+# ---- threshold signatures: ThresholdSign, the coin of BinaryAgreement ----
+def g2_points_prepare(g2, stream=None):
+    """Decode and check G2 points (uint8 [n, 192]) once -- the received
+    signature shares, which differ per check and so cannot be prepared lines.
+    Returns the device table (uint8) for sig_check_prepared and the G2
+    combine."""
+    torch = _torch()
+    n = g2.shape[0]
+    assert g2.shape == (n, G2_BYTES) and g2.is_contiguous()
+    tab = torch.empty(lib().hbrbc_g2_points_size(n), dtype=torch.uint8, device=g2.device)
+    _check(lib().hbrbc_g2_points_prepare(g2.data_ptr(), n, tab.data_ptr(),
+                                         _stream(g2.device, stream)))
+    return tab
+
+
+def sig_check_prepared(sig_tab, sig_count, keys, key_points, idx_key, prep, points, idx_h,
+                       ws=None, stream=None):
+    """`PublicKeyShare::verify_g2` for sig_count shares: check i is
+    e(K[idx_key[i]], P[idx_h[i]]) == e(G1::one(), S[i]) with S = sig_tab
+    (g2_points_prepare over exactly `sig_count` shares), K = `key_points` keys
+    (g1_prepare), P = `points` prepared G2 points (g2_prepare: the hashes);
+    idx_* int32 [sig_count].  Returns uint8 [sig_count]: 1 equal, 0 not, 2
+    invalid point or index."""
+    torch = _torch()
+    count = sig_count
+    for t in (idx_key, idx_h):
+        assert t.shape == (count,) and t.dtype == torch.int32 and t.is_contiguous()
+    assert sig_tab.numel() == lib().hbrbc_g2_points_size(sig_count)
+    assert keys.numel() == lib().hbrbc_g1_prepared_size(key_points)
+    assert prep.numel() == lib().hbrbc_g2_prepared_size(points)
+    ok = torch.empty((count,), dtype=torch.uint8, device=sig_tab.device)
+    if ws is None:
+        ws = workspace(count, sig_tab.device.index)
+    assert ws.numel() >= lib().hbrbc_pairing_workspace_size(count)
+    _check(lib().hbrbc_sig_check_prepared(
+        sig_tab.data_ptr(), sig_count, keys.data_ptr(), key_points, idx_key.data_ptr(),
+        prep.data_ptr(), points, idx_h.data_ptr(), count, ok.data_ptr(), ws.data_ptr(),
+        _stream(sig_tab.device, stream)))
+    return ok
+
+
+def combine_g2_workspace(total_shares, groups, device=0):
+    """Device workspace for combining `total_shares` G2 shares in `groups` groups."""
+    torch = _torch()
+    n = lib().hbrbc_g2_combine_workspace_size(total_shares, groups)
+    return torch.empty(max(n, 1), dtype=torch.uint8, device="cuda:%d" % device)
+
+
+def _g2_combine_outputs(groups, device):
+    torch = _torch()
+    return (torch.empty((groups, G2_BYTES), dtype=torch.uint8, device=device),
+            torch.empty((groups, G2_COMPRESSED_BYTES), dtype=torch.uint8, device=device),
+            torch.empty((groups,), dtype=torch.uint8, device=device),
+            torch.empty((groups,), dtype=torch.uint8, device=device))
+
+
+def g2_lincomb_prepared(sig_tab, sig_count, rows, scalars, offsets, ws=None, stream=None):
+    """Per group sum_j scalars[j] * S[rows[j]] over S = sig_tab, a
+    g2_points_prepare table of exactly `sig_count` points: rows int32 [total],
+    scalars uint8 [total, 32] (big-endian, < r), offsets int32 [groups + 1].
+    Returns (out192 uint8 [groups, 192], out96 uint8 [groups, 96] compressed,
+    parity uint8 [groups], status uint8 [groups]: 0 ok, 1 infinity, 2 invalid
+    input; failed groups are zero bytes)."""
+    torch = _torch()
+    assert sig_tab.numel() == lib().hbrbc_g2_points_size(sig_count)
+    assert rows.dtype == torch.int32 and rows.dim() == 1
+    assert scalars.dtype == torch.uint8 and scalars.shape == (rows.shape[0], FR_BYTES)
+    groups, total = _ragged(offsets, rows, scalars)
+    assert sig_tab.device == rows.device
+    out192, out96, par, st = _g2_combine_outputs(groups, rows.device)
+    if ws is None:
+        ws = combine_g2_workspace(total, groups, rows.device.index)
+    assert ws.numel() >= lib().hbrbc_g2_combine_workspace_size(total, groups)
+    _check(lib().hbrbc_g2_lincomb_prepared(
+        sig_tab.data_ptr(), sig_count, rows.data_ptr(), scalars.data_ptr(), offsets.data_ptr(),
+        groups, out192.data_ptr(), out96.data_ptr(), par.data_ptr(), st.data_ptr(), ws.data_ptr(),
+        _stream(rows.device, stream)))
+    return out192, out96, par, st
+
+
+def sig_combine_prepared(sig_tab, sig_count, rows, idx, offsets, ws=None, stream=None):
+    """`combine_signatures` for ragged groups of shares: share j is row rows[j]
+    of sig_tab (a g2_points_prepare table of exactly `sig_count` points) and
+    comes from node idx[j]; rows, idx int32 [total], offsets int32 [groups +
+    1].  Returns (out192, out96, parity, status) as g2_lincomb_prepared, with
+    status 3 for a group that repeats an index."""
+    torch = _torch()
+    assert sig_tab.numel() == lib().hbrbc_g2_points_size(sig_count)
+    assert rows.dtype == torch.int32 and rows.dim() == 1
+    assert idx.dtype == torch.int32 and idx.dim() == 1
+    groups, total = _ragged(offsets, rows, idx)
+    assert sig_tab.device == rows.device
+    out192, out96, par, st = _g2_combine_outputs(groups, rows.device)
+    if ws is None:
+        ws = combine_g2_workspace(total, groups, rows.device.index)
+    assert ws.numel() >= lib().hbrbc_g2_combine_workspace_size(total, groups)
+    _check(lib().hbrbc_sig_combine_prepared(
+        sig_tab.data_ptr(), sig_count, rows.data_ptr(), idx.data_ptr(), offsets.data_ptr(),
+        groups, out192.data_ptr(), out96.data_ptr(), par.data_ptr(), st.data_ptr(), ws.data_ptr(),
+        _stream(rows.device, stream)))
+    return out192, out96, par, st
+
+
+def _sig_results(out192, out96, par, st):
+    o192, o96 = out192.cpu().numpy(), out96.cpu().numpy()
+    parh, sth = par.cpu().tolist(), st.cpu().tolist()
+    return [(bytes(o192[g]), bytes(o96[g]), parh[g]) if s in (COMBINE_OK, COMBINE_INFINITY)
+            else None for g, s in enumerate(sth)]
+
+
+def _need_gpu():
+    lib()
+    if not _torch().cuda.is_available():
+        raise HbrbcUnavailable("no HIP device visible")
+
+
+def _g2_rows(points, dev):
+    import numpy as np
+    for p in points:
+        if len(p) != G2_BYTES:
+            raise ValueError("G2 encoding of %d bytes, expected %d" % (len(p), G2_BYTES))
+    a = np.empty((len(points), G2_BYTES), np.uint8)
+    for r, p in enumerate(points):
+        a[r] = np.frombuffer(p, np.uint8)
+    return _torch().from_numpy(a).to(dev)
+
+
+def _g1_rows(points, dev):
+    import numpy as np
+    for p in points:
+        if len(p) != G1_BYTES:
+            raise ValueError("G1 encoding of %d bytes, expected %d" % (len(p), G1_BYTES))
+    a = np.empty((len(points), G1_BYTES), np.uint8)
+    for r, p in enumerate(points):
+        a[r] = np.frombuffer(p, np.uint8)
+    return _torch().from_numpy(a).to(dev)
+
+
+def _dedup(values):
+    """(distinct values in first-seen order, the position of each input)."""
+    ids = {}
+    pos = [ids.setdefault(bytes(v), len(ids)) for v in values]
+    return list(ids), pos
+
+
+def verify_signature_shares(items, device=0):
+    """Batched `PublicKeyShare::verify_g2` (threshold_sign.rs:216-225): items =
+    [(share G2, pk_share G1, hash G2)] host bytes.  Each distinct hash and key
+    is prepared once.  Returns a list of bools (an invalid point is False)."""
+    import numpy as np
+    torch = _torch()
+    if not items:
+        return []
+    _need_gpu()
+    dev = "cuda:%d" % device
+    keys, ik = _dedup([pk for _, pk, _ in items])
+    hashes, ih = _dedup([h for _, _, h in items])
+    stab = g2_points_prepare(_g2_rows([s for s, _, _ in items], dev))
+    ktab = g1_prepare(_g1_rows(keys, dev))
+    prep = g2_prepare(_g2_rows(hashes, dev))
+    ok = sig_check_prepared(stab, len(items), ktab, len(keys),
+                            torch.from_numpy(np.asarray(ik, np.int32)).to(dev), prep, len(hashes),
+                            torch.from_numpy(np.asarray(ih, np.int32)).to(dev))
+    return [v == CHECK_OK for v in ok.cpu().tolist()]
+
+
+def combine_signature_shares(groups, device=0):
+    """`combine_signatures` for host bytes: groups = [[(node index, share
+    G2)]].  Returns per group (signature uncompressed 192 bytes, compressed 96
+    bytes, parity 0 / 1), or None for a group with an invalid share or a
+    repeated index."""
+    import numpy as np
+    torch = _torch()
+    if not groups:
+        return []
+    _need_gpu()
+    dev = "cuda:%d" % device
+    flat = [item for grp in groups for item in grp]
+    total = len(flat)
+    offs = np.zeros(len(groups) + 1, np.int32)
+    offs[1:] = np.cumsum([len(grp) for grp in groups])
+    tab = g2_points_prepare(_g2_rows([s for _, s in flat], dev))
+    out = sig_combine_prepared(tab, total, torch.arange(total, dtype=torch.int32, device=dev),
+                               _u32_tensor([i for i, _ in flat], dev),
+                               torch.from_numpy(offs).to(dev))
+    return _sig_results(*out)
+
+
+def sig_combine(shares):
+    """Per-call shim: one group [(node index, share G2)] of host bytes through
+    hbrbc_sig_combine (one device round trip).  Returns (sig192, sig96,
+    parity); raises RseError(InvalidArgument) on an invalid share or a repeated
+    index."""
+    import numpy as np
+    for _, share in shares:
+        if len(share) != G2_BYTES:
+            raise ValueError("share of %d bytes, expected %d" % (len(share), G2_BYTES))
+    idx = np.asarray([i for i, _ in shares], dtype=np.uint32)
+    o192 = ctypes.create_string_buffer(G2_BYTES)
+    o96 = ctypes.create_string_buffer(G2_COMPRESSED_BYTES)
+    par = ctypes.create_string_buffer(1)
+    _check(lib().hbrbc_sig_combine(b"".join(bytes(s) for _, s in shares), idx.ctypes.data,
+                                   len(shares), o192, o96, par))
+    return o192.raw, o96.raw, par.raw[0]
+
+
+def threshold_sign_grouped(documents, shares, threshold, public_key, device=0):
+    """The whole of `ThresholdSign` for many coins: documents = [hash G2],
+    shares = [(document index, node index, share G2, pk_share G1)].  Each hash
+    and each distinct pk_i is prepared once and the shares are decoded once (on
+    side streams); all shares are checked; each document then combines its
+    first `threshold + 1` valid shares in ascending node index (the order of
+    the BTreeMap in combine_and_verify_sig; a node counts once) straight from
+    the share table, and every combined signature is checked against
+    `public_key` through the same check kernel.  Returns (bools in the order of
+    `shares`, per document (sig192, sig96, parity, verified) or None with fewer
+    than threshold + 1 valid shares)."""
+    import numpy as np
+    torch = _torch()
+    if len(public_key) != G1_BYTES:
+        raise ValueError("public key of %d bytes, expected %d" % (len(public_key), G1_BYTES))
+    _need_gpu()
+    outs = [None] * len(documents)
+    if not shares:
+        return [], outs
+    dev = "cuda:%d" % device
+    # the public key is key 0 of the table, the validators' keys follow
+    keys, ik = _dedup([public_key] + [pk for _, _, _, pk in shares])
+    order = sorted(range(len(shares)), key=lambda i: shares[i][0])
+    d2 = _g2_rows(documents, dev)
+    dk = _g1_rows(keys, dev)
+    ds = _g2_rows([shares[i][2] for i in order], dev)
+    ih = np.asarray([shares[i][0] for i in order], np.int32)
+    ic = np.asarray([ik[1 + i] for i in order], np.int32)
+    # three independent preparations, each on a stream of its own (see
+    # _verify_grouped); the checks wait for all three
+    cur = torch.cuda.current_stream(dev)
+    sides = [torch.cuda.Stream(dev) for _ in range(3)]
+    for s_ in sides:
+        s_.wait_stream(cur)
+    with torch.cuda.stream(sides[0]):
+        prep = g2_prepare(d2)
+    with torch.cuda.stream(sides[1]):
+        ktab = g1_prepare(dk)
+    with torch.cuda.stream(sides[2]):
+        stab = g2_points_prepare(ds)
+    for s_ in sides:
+        cur.wait_stream(s_)
+    for t_, s_ in ((d2, sides[0]), (dk, sides[1]), (ds, sides[2])):
+        t_.record_stream(s_)
+    for t_ in (prep, ktab, stab):
+        t_.record_stream(cur)
+    okh = sig_check_prepared(stab, len(shares), ktab, len(keys), torch.from_numpy(ic).to(dev),
+                             prep, len(documents), torch.from_numpy(ih).to(dev)).cpu().tolist()
+    flags = [False] * len(shares)
+    valid = [[] for _ in documents]   # per document: (node index, table row)
+    for r, i in enumerate(order):
+        flags[i] = okh[r] == CHECK_OK
+        if flags[i]:
+            valid[shares[i][0]].append((shares[i][1], r))
+    rows, idx, offs, docs = [], [], [0], []
+    for d, cand in enumerate(valid):
+        seen, pick = set(), []
+        for node, r in sorted(cand):
+            if node not in seen:
+                seen.add(node)
+                pick.append((node, r))
+        if len(pick) < threshold + 1:
+            continue
+        pick = pick[:threshold + 1]
+        rows += [r for _, r in pick]
+        idx += [node for node, _ in pick]
+        offs.append(len(rows))
+        docs.append(d)
+    if docs:
+        o192, o96, par, st = sig_combine_prepared(
+            stab, len(shares), torch.from_numpy(np.asarray(rows, np.int32)).to(dev),
+            _u32_tensor(idx, dev), torch.from_numpy(np.asarray(offs, np.int32)).to(dev))
+        # the combined signatures, still on the device, become a share table of
+        # their own: e(public_key, H_d) == e(G1::one(), sig_d)
+        ctab = g2_points_prepare(o192)
+        ver = sig_check_prepared(ctab, len(docs), ktab, len(keys),
+                                 torch.zeros(len(docs), dtype=torch.int32, device=dev), prep,
+                                 len(documents),
+                                 torch.from_numpy(np.asarray(docs, np.int32)).to(dev))
+        verh = ver.cpu().tolist()
+        for j, (d, res) in enumerate(zip(docs, _sig_results(o192, o96, par, st))):
+            if res is not None:
+                outs[d] = res + (verh[j] == CHECK_OK,)
     return flags, outs
 
 

@@ -553,6 +553,71 @@ int hbrbc_decrypt_combine_prepared(const void *a_prepared, size_t prepared_count
 int hbrbc_decrypt_combine(const uint8_t *shares, const uint32_t *idx, size_t n, uint8_t out96[96],
                           uint8_t out48[48]);
 
+/* ---- threshold signatures: ThresholdSign, the coin of BinaryAgreement ----
+ * `ThresholdSign` (threshold_sign.rs; binary_agreement.rs:444-446 creates one
+ * per coin round and :404 takes `sig.parity()` as the coin) checks every
+ * received share with
+ *   `PublicKeyShare::verify_g2`           e(pk_i, H) == e(G1::one(), share_i)
+ * (:216-225, H = hash_g2(doc)) and, with more than num_faulty valid shares,
+ * runs `combine_signatures` -- the Lagrange interpolation at 0 of the shares
+ * in G2 -- and checks the result against the master public key (:249-270) in
+ * the same form.  hash_g2 (a ChaCha-seeded G2 sample) stays with the caller,
+ * like hash_g1_g2: H arrives as a G2 point.  Shares arrive in the uncompressed
+ * encoding (192 bytes); decompressing 96-byte wire shares is the caller's.
+ *
+ * The G2 point on the right of the check differs per share, so it is not a
+ * prepared-lines point: the shares are decoded and checked once (canonical
+ * coordinates, on the twist, order r) into a point table, which both the
+ * check and the combine read.  Device memory, async on `stream`. */
+#define HBRBC_G2_COMPRESSED_BYTES 96
+/* Bytes of a table of `points` decoded G2 points. */
+size_t hbrbc_g2_points_size(size_t points);
+/* Decodes g2 (count x 192 bytes) into `table` (hbrbc_g2_points_size(count)
+ * bytes): affine coordinates and a status per point (invalid points are kept
+ * as status, their coordinates zero). */
+int hbrbc_g2_points_prepare(const uint8_t *g2, size_t count, void *table, void *stream);
+/* count checks e(K[idx_key[i]], P[idx_h[i]]) == e(G1::one(), S[i]): S = a
+ * hbrbc_g2_points_prepare table of exactly `sig_count` points (check i reads
+ * entry i), K = `key_points` keys of hbrbc_g1_prepare, P = `points` points of
+ * hbrbc_g2_prepare.  ok_out[i]: 1 equal, 0 not, 2 an invalid point, an index
+ * outside its table or i >= sig_count.  An S[i] at infinity is a valid point
+ * (the check then holds only if the left side is 1).  Workspace:
+ * hbrbc_pairing_workspace_size(count). */
+int hbrbc_sig_check_prepared(const void *sig_table, size_t sig_count, const void *keys,
+                             size_t key_points, const uint32_t *idx_key, const void *prepared,
+                             size_t points, const uint32_t *idx_h, size_t count, uint8_t *ok_out,
+                             void *workspace, void *stream);
+/* Combining signature shares: ragged groups and statuses as for the
+ * decryption shares above.  Results per group: out192 + 192 g the uncompressed
+ * encoding, out96 + 96 g zkcrypto's G2Compressed (x.c1 || x.c0 big-endian with
+ * 0x80 set in byte 0, 0x20 set iff y is the larger of y and -y, c1 compared
+ * first and c0 only when the c1 are equal; infinity = 0xC0 and 95 zero
+ * bytes), parity_out[g] the XOR of all bits of the uncompressed encoding
+ * (`Signature::parity()`, the coin).  For statuses 2 and 3 all three are zero
+ * bytes.  Device workspace bytes of the two entries below: */
+size_t hbrbc_g2_combine_workspace_size(size_t total_shares, size_t groups);
+/* Per group sum_j scalars[j] * S[rows[j]] over a table S of
+ * hbrbc_g2_points_prepare with exactly `sig_count` points: rows int32 per
+ * share, scalars 32 big-endian bytes per share (>= r: status 2). */
+int hbrbc_g2_lincomb_prepared(const void *sig_table, size_t sig_count, const int32_t *rows,
+                              const uint8_t *scalars, const uint32_t *offsets, size_t groups,
+                              uint8_t *out192, uint8_t *out96, uint8_t *parity_out,
+                              uint8_t *status_out, void *workspace, void *stream);
+/* `combine_signatures`: the Lagrange coefficients of idx (as
+ * hbrbc_lagrange_coeffs) followed by the linear combination, share j of a
+ * group being S[rows[j]] from node idx[j]; status 3 for a repeated index. */
+int hbrbc_sig_combine_prepared(const void *sig_table, size_t sig_count, const int32_t *rows,
+                               const uint32_t *idx, const uint32_t *offsets, size_t groups,
+                               uint8_t *out192, uint8_t *out96, uint8_t *parity_out,
+                               uint8_t *status_out, void *workspace, void *stream);
+/* Per-call shim on host memory (one group of n shares, 192 bytes each, from
+ * nodes idx[0..n); synchronous, current device): decodes and checks the
+ * shares and combines them.  HBRBC_E_INVALID_ARG for an invalid share or a
+ * repeated index (statuses 2 and 3); a result at infinity is returned in its
+ * encodings. */
+int hbrbc_sig_combine(const uint8_t *shares, const uint32_t *idx, size_t n, uint8_t out192[192],
+                      uint8_t out96[96], uint8_t *parity);
+
 /* ---- the Broadcast state machine, batched --------------- */
 /* Many instances x nodes of `Broadcast` (broadcast.rs:228-558) in synchronous
  * rounds: what a node emits in round t is delivered in round t + 1, each node

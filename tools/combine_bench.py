@@ -40,10 +40,11 @@ KERNELS = {"lagrange": "lagrange_kernel", "scalar_mul": "g1_scalar_mul_kernel",
 MODEL_RATIO = (0.05, 0.06)
 
 
-def kernel_resources(lib_path):
-    """{kernel: {scratch_bytes, vgprs, vgpr_spills}} of the combine kernels,
-    from the gfx950 code objects bundled in the library; None without
-    llvm-readelf."""
+def kernel_resources(lib_path, kernels=None):
+    """{kernel: {scratch_bytes, vgprs, vgpr_spills}} of the combine kernels (or
+    of `kernels`, {key: kernel name}), from the gfx950 code objects bundled in
+    the library; None without llvm-readelf."""
+    kernels = kernels or KERNELS
     readelf = "/opt/rocm/llvm/bin/llvm-readelf"
     if not os.path.exists(readelf):
         return None
@@ -69,7 +70,7 @@ def kernel_resources(lib_path):
             for line in notes.splitlines() + ["  - end"]:
                 line = line.strip()
                 if line.startswith("- "):       # next kernel's record
-                    for key, name in KERNELS.items():
+                    for key, name in kernels.items():
                         if name in cur.get(".name", ""):
                             out[key] = {"scratch_bytes": int(cur[".private_segment_fixed_size"]),
                                         "vgprs": int(cur[".vgpr_count"]),
