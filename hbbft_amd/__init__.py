@@ -166,6 +166,10 @@ def lib():
                                                       _P]),
         "hbrbc_sig_combine": (ctypes.c_int, [ctypes.c_char_p, _P, _S, ctypes.c_char_p,
                                              ctypes.c_char_p, ctypes.c_char_p]),
+        "hbrbc_g1_prepare_compressed": (ctypes.c_int, [_P, _S, _P, _P]),
+        "hbrbc_g2_points_prepare_compressed": (ctypes.c_int, [_P, _S, _P, _P]),
+        "hbrbc_g1_decompress": (ctypes.c_int, [_P, _S, _P, _P, _P]),
+        "hbrbc_g2_decompress": (ctypes.c_int, [_P, _S, _P, _P, _P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -2561,6 +2561,46 @@ int hbrbc_g2_points_prepare(const uint8_t *g2, size_t count, void *table, void *
     return HBRBC_OK;
 }
 
+// ---- compressed wire encodings (pairing.hip) -------------------------------
+int hbrbc_g1_prepare_compressed(const uint8_t *g1c, size_t count, void *prepared, void *stream) {
+    if (count == 0) return HBRBC_OK;
+    if (!g1c || !prepared) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    uint32_t *keys = static_cast<uint32_t *>(prepared);
+    uint8_t *kst = static_cast<uint8_t *>(prepared) + round_up(g1_key_words(count) * 4, 256);
+    HB_HIP(launch_g1_prepare_compressed(g1c, count, keys, kst, static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
+int hbrbc_g2_points_prepare_compressed(const uint8_t *g2c, size_t count, void *table,
+                                       void *stream) {
+    if (count == 0) return HBRBC_OK;
+    if (!g2c || !table) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_g2_points_compressed(g2c, count, static_cast<uint32_t *>(table),
+                                       const_cast<uint8_t *>(g2_points_status(table, count)),
+                                       static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
+int hbrbc_g1_decompress(const uint8_t *g1c, size_t count, uint8_t *out96, uint8_t *status,
+                        void *stream) {
+    if (count == 0) return HBRBC_OK;
+    if (!g1c || !out96 || !status) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_g1_decompress(g1c, count, out96, status, static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
+int hbrbc_g2_decompress(const uint8_t *g2c, size_t count, uint8_t *out192, uint8_t *status,
+                        void *stream) {
+    if (count == 0) return HBRBC_OK;
+    if (!g2c || !out192 || !status) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_g2_decompress(g2c, count, out192, status, static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
 int hbrbc_sig_check_prepared(const void *sig_table, size_t sig_count, const void *keys,
                              size_t key_points, const uint32_t *idx_key, const void *prepared,
                              size_t points, const uint32_t *idx_h, size_t count, uint8_t *ok_out,

@@ -23,6 +23,12 @@ Threshold signatures (the G2 share check and combine): G1::one(), whose
 negative is the constant G1 point of every check e(pk, H) == e(G1::one(), sig),
 and gamma = N(xi^-((p-1)/3)) in Fp with psi^2(x, y) = (gamma x, -y) = [x^2] Q on
 G2 (no sign flip, unlike phi on G1); main() asserts gamma against psi o psi.
+
+Compressed encodings (decompress_g1 / decompress_g2): p = 3 mod 4, so for a
+square a the power t = a^((p-3)/4) is 1/sqrt(a) and t a the root; kSqrtExp is
+that exponent as plain limbs (fp_pow_sqrt walks it in 4-bit windows, top
+window first, which main() asserts to be non-zero) and kHalf = 1/2, for the
+(a0 + |a|)/2 of the square root in Fp2 by norms.
 """
 P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
 X_ABS = 0xd201000000010000
@@ -32,6 +38,10 @@ RM_FR = 1 << 256   # 8 rounds of 32 bits (pairing.hip fr_mul)
 # G1::one(), the standard generator (affine x, y)
 G1_X = 0x17f1d3a73197d7942695638c4fa9ac0fc3688c4f9774b905a14e3a3f171bac586c55e83ff97a1aeffb3af00adb22c6bb
 G1_Y = 0x08b3f481e3aaa0f1a09e30ed741d8ae4fcf5e095d5d00af600db18cb2c04b3edd03cc744a2888ae40caa232946c5e7e1
+
+
+SQRT_EXP = (P - 3) // 4
+SQRT_WINDOWS = (SQRT_EXP.bit_length() + 3) // 4
 
 
 def limbs(v):
@@ -117,6 +127,8 @@ def fp2_arr(name, vals):
 def main():
     xi = (1, 1)
     assert (G1_Y * G1_Y - G1_X ** 3 - 4) % P == 0
+    assert P % 4 == 3 and SQRT_EXP >> (4 * (SQRT_WINDOWS - 1)) != 0
+    assert pow(9, SQRT_EXP, P) * 3 % P in (1, P - 1)   # 1/sqrt(9) = +-1/3
     inv29 = (-pow(P, -1, 1 << 29)) % (1 << 29)
     out = [
         "// Generated by gen_bls_consts.py -- BLS12-381 constants for pairing.hip.",
@@ -150,6 +162,9 @@ def main():
         arr("kG1GenX", mont(G1_X)) + "  // G1::one(), affine x",
         arr("kG1GenNegY", mont(P - G1_Y)) + "  // -G1::one(): p - y",
         arr("kGammaG2", mont(gamma_g2())) + "  // G2: psi^2(x, y) = (gamma x, -y) = [x^2] Q",
+        arr("kSqrtExp", SQRT_EXP) + "  // (p - 3) / 4, plain: a^this = 1/sqrt(a)",
+        "constexpr int kSqrtExpWindows = %d;  // 4-bit windows of kSqrtExp" % SQRT_WINDOWS,
+        arr("kHalf", mont((P + 1) // 2)) + "  // 1/2",
         "}}  // namespace hbrbc::bls",
     ]
     print("\n".join(out))

@@ -301,6 +301,17 @@ hipError_t launch_g2_reduce_encode(const uint32_t *ws, const uint8_t *pst, const
                                    size_t groups, size_t total, const uint8_t *lst,
                                    uint8_t *out192, uint8_t *out96, uint8_t *parity,
                                    uint8_t *status, hipStream_t s);
+// compressed wire encodings (pairing.hip): the g1_prepare / g2_points tables
+// from 48- / 96-byte points, and compressed to uncompressed bytes with a
+// status byte per point (0 ok, 1 infinity, 2 invalid)
+hipError_t launch_g1_prepare_compressed(const uint8_t *g1c, size_t count, uint32_t *keys,
+                                        uint8_t *kst, hipStream_t s);
+hipError_t launch_g2_points_compressed(const uint8_t *g2c, size_t count, uint32_t *tab,
+                                       uint8_t *gst, hipStream_t s);
+hipError_t launch_g1_decompress(const uint8_t *g1c, size_t count, uint8_t *out96, uint8_t *status,
+                                hipStream_t s);
+hipError_t launch_g2_decompress(const uint8_t *g2c, size_t count, uint8_t *out192,
+                                uint8_t *status, hipStream_t s);
 
 hipError_t configure_kernels();
 

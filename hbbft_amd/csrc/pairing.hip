@@ -2196,6 +2196,240 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
     status[g] = (uint8_t)st;
 }
 
+// ------------------------------------------------- compressed encodings
+// hbbft's messages carry every point in the crate's compressed form: 48 bytes
+// for G1 (DecryptionShare, PublicKeyShare, a ciphertext's U), 96 for G2
+// (SignatureShare, a ciphertext's W) -- x big-endian (G2: x.c1 || x.c0) with
+// three flag bits in byte 0: 0x80 compressed (must be set), 0x40 infinity
+// (then every other bit must be zero), 0x20 "y is the larger of y and -y".
+// decompress_g1 / decompress_g2 restate the `pairing` crate's
+// G1Compressed::into_affine / G2Compressed::into_affine: flags, x < p,
+// y = sqrt(x^3 + b) (no root: invalid), the choice between y and -y by the
+// comparison the two encode kernels above apply, then the order-r check.
+//
+// p = 3 mod 4: for a square a, t = a^((p-3)/4) is 1/sqrt(a) and t a the root.
+// The exponent is a constant (kSqrtExp, 379 bits), walked in 4-bit windows:
+// 14 products for a^1 .. a^15, then 4 squarings and at most one product per
+// window -- 376 squarings and 89 products, a third of the products of
+// g1_in_subgroup's 127 doublings and 64 additions.  The digit is
+// wave-uniform, so the table is indexed by a scalar and the skipped product of
+// a zero digit is a uniform branch; the table itself (15 x 12 words) lives in
+// scratch beside the stack of the NOINL units, read once per window.
+NOINL void fp_pow_sqrt(Fp &r, const Fp &a) {
+    Fp tab[15];
+    tab[0] = a;
+    for (int i = 1; i < 15; ++i) fp_mul(tab[i], tab[i - 1], a);
+    constexpr int top = kSqrtExpWindows - 1;
+    constexpr uint32_t topd = (kSqrtExp[top >> 3] >> (4 * (top & 7))) & 15u;
+    static_assert(topd != 0, "the top window holds the exponent's leading bits");
+    Fp acc = tab[topd - 1];
+    for (int w = top - 1; w >= 0; --w) {
+#pragma unroll 1
+        for (int k = 0; k < 4; ++k) fp_sqr(acc, acc);
+        const uint32_t d = (kSqrtExp[w >> 3] >> (4 * (w & 7))) & 15u;
+        if (d) fp_mul(acc, acc, tab[d - 1]);
+    }
+    r = acc;
+}
+
+// sign of y - (-y) as integers for a canonical (non-Montgomery) y, -0 = 0:
+// the comparison of g1_reduce_encode_kernel / g2_reduce_encode_kernel
+DEV int fp_cmp_neg(const Fp &yc) {
+    Fp nc;
+    uint32_t br = 0;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) nc.l[i] = subb(kP[i], yc.l[i], br, &br);
+    if (fp_is_zero(yc)) nc = yc;
+    int cmp = 0;
+#pragma unroll
+    for (int i = NL - 1; i >= 0; --i)
+        if (cmp == 0 && yc.l[i] != nc.l[i]) cmp = yc.l[i] > nc.l[i] ? 1 : -1;
+    return cmp;
+}
+
+DEV int decompress_g1(const uint8_t *src, Fp &x, Fp &y) {
+    const uint8_t f = src[0];
+    if (!(f & 0x80)) return PT_BAD;                    // not a compressed encoding
+    if (f & 0x40) return all_zero(src, 48, 0x3F) ? PT_INF : PT_BAD;
+    Fp xr;
+    if (!load_be48(xr, src, 0x1FFFFFFFu)) return PT_BAD;
+    to_mont(x, xr);
+    Fp a, b, t, c;
+    fp_sqr(a, x);
+    fp_mul(a, a, x);
+    fp_set(b, kB1);
+    fp_add(a, a, b);                                   // x^3 + 4
+    fp_pow_sqrt(t, a);
+    fp_mul(y, t, a);
+    fp_sqr(c, y);
+    if (!fp_eq(c, a)) return PT_BAD;                   // y^2 = x^3 + 4, or no root
+    from_mont(c, y);
+    if ((fp_cmp_neg(c) > 0) != ((f & 0x20) != 0)) fp_neg(y, y);
+    return g1_in_subgroup(x, y) ? PT_OK : PT_BAD;
+}
+
+// Square root in Fp2 by norms: two exponentiations in Fp and no retry.  With
+// d = sqrt(a0^2 + a1^2) (a square in Fp iff a is one in Fp2) and
+// delta = (a0 + d)/2, t = delta^((p-3)/4) and x0 = t delta: either x0^2 =
+// delta, then t = 1/x0 and the root is x0 + a1/(2 x0) u; or x0^2 = -delta
+// (delta is no square, so (a0 - d)/2 = a1^2 / (4 x0^2) is one), then -t =
+// 1/x0 and the root is a1/(2 x0) + x0 u.  delta = 0 only for a1 = 0 and d =
+// -a0, where (a0 - d)/2 = a0 takes its place.  Returns whether y^2 == a,
+// checked on the result itself: a non-square norm gives some d, t and a y
+// that fails here.
+NOINL bool fp2_sqrt(Fp2 &y, const Fp2 &a) {
+    Fp n, t, d, h, delta, x0, x1, c;
+    fp_sqr(n, a.c0);
+    fp_sqr(t, a.c1);
+    fp_add(n, n, t);
+    fp_pow_sqrt(t, n);
+    fp_mul(d, t, n);
+    fp_set(h, kHalf);
+    fp_add(delta, a.c0, d);
+    fp_mul(delta, delta, h);
+    if (fp_is_zero(delta)) delta = a.c0;
+    fp_pow_sqrt(t, delta);
+    fp_mul(x0, t, delta);
+    fp_sqr(c, x0);
+    const bool res = fp_eq(c, delta);
+    fp_mul(x1, a.c1, t);
+    fp_mul(x1, x1, h);                                 // +- a1 / (2 x0)
+    if (res) {
+        y.c0 = x0;
+        y.c1 = x1;
+    } else {
+        fp_neg(y.c0, x1);
+        y.c1 = x0;
+    }
+    Fp2 s;
+    fp2_sqr(s, y);
+    return fp2_eq(s, a);
+}
+
+DEV int decompress_g2(const uint8_t *src, Fp2 &x, Fp2 &y) {
+    const uint8_t f = src[0];
+    if (!(f & 0x80)) return PT_BAD;
+    if (f & 0x40) return all_zero(src, 96, 0x3F) ? PT_INF : PT_BAD;
+    Fp a, b;
+    if (!load_be48(a, src, 0x1FFFFFFFu) || !load_be48(b, src + 48, 0xFFFFFFFFu)) return PT_BAD;
+    to_mont(x.c1, a);
+    to_mont(x.c0, b);
+    Fp2 r, bb;
+    fp2_sqr(r, x);
+    fp2_mul(r, r, x);
+    fp_set(bb.c0, kB1);
+    bb.c1 = bb.c0;                                     // 4 (u + 1)
+    fp2_add(r, r, bb);
+    if (!fp2_sqrt(y, r)) return PT_BAD;
+    from_mont(a, y.c1);
+    from_mont(b, y.c0);
+    int cmp = fp_cmp_neg(a);                           // c1 first, c0 when the c1 are equal
+    if (cmp == 0) cmp = fp_cmp_neg(b);
+    if ((cmp > 0) != ((f & 0x20) != 0)) fp2_neg(y, y);
+    return g2_in_subgroup(x, y) ? PT_OK : PT_BAD;
+}
+
+// g1_prepare_kernel for compressed input (48 bytes per point): the same table.
+// Waves per SIMD: 2 like g1_prepare_kernel.  hipcc -S: 248 VGPRs, no spills,
+// 944 bytes of scratch -- the 272 of g1_prepare_kernel (the stack of the NOINL
+// units: pt_dbl and pt_add_affine take their operands by reference, so no
+// occupancy frees that kernel of scratch either) and the window table, which
+// is indexed by the digit and so could stay in registers only fully unrolled.
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_prepare_compressed_kernel(
+    const uint8_t *__restrict__ g1c, size_t count, uint32_t *__restrict__ keys,
+    uint8_t *__restrict__ kst) {
+    const size_t q = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (q >= count) return;
+    Fp x, y;
+    const int st = decompress_g1(g1c + q * 48, x, y);
+    if (st != PT_OK) {
+        fp_zero(x);
+        fp_zero(y);
+    }
+    uint32_t *dst = keys + q * kG1KeyWords;
+#pragma unroll
+    for (int w = 0; w < NL; w += 4) {
+        *reinterpret_cast<uint4 *>(dst + w) = make_uint4(x.l[w], x.l[w + 1], x.l[w + 2], x.l[w + 3]);
+        *reinterpret_cast<uint4 *>(dst + NL + w) = make_uint4(y.l[w], y.l[w + 1], y.l[w + 2], y.l[w + 3]);
+    }
+    kst[q] = (uint8_t)st;
+}
+
+// g2_points_kernel for compressed input (96 bytes per point): the same table.
+// Waves per SIMD: 2 like g2_points_kernel: the Fp2 chain of g2_in_subgroup
+// sets the register need, the Fp roots add none (hipcc -S: 256 VGPRs, 2
+// spilled, 1572 bytes of scratch against 4 and 1684 of g2_points_kernel).
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void g2_points_compressed_kernel(
+    const uint8_t *__restrict__ g2c, size_t count, uint32_t *__restrict__ tab,
+    uint8_t *__restrict__ gst) {
+    const size_t q = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (q >= count) return;
+    Fp2 x, y;
+    const int st = decompress_g2(g2c + q * 96, x, y);
+    if (st != PT_OK) {
+        fp2_zero(x);
+        fp2_zero(y);
+    }
+    const Fp *v[4] = {&x.c0, &x.c1, &y.c0, &y.c1};
+    uint32_t *dst = tab + q * kG2PtWords;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int w = 0; w < NL; w += 4)
+            *reinterpret_cast<uint4 *>(dst + e * NL + w) =
+                make_uint4(v[e]->l[w], v[e]->l[w + 1], v[e]->l[w + 2], v[e]->l[w + 3]);
+    gst[q] = (uint8_t)st;
+}
+
+// Compressed to uncompressed, one lane per point: out96 + 96 q gets x || y
+// (zero bytes for an invalid point, 0x40 and zeros for infinity), status[q]
+// 0 ok, 1 infinity, 2 invalid.  For points that go on to an entry taking the
+// uncompressed form (a ciphertext's U and W).
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_decompress_kernel(
+    const uint8_t *__restrict__ g1c, size_t count, uint8_t *__restrict__ out96,
+    uint8_t *__restrict__ status) {
+    const size_t q = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (q >= count) return;
+    Fp x, y;
+    const int st = decompress_g1(g1c + q * 48, x, y);
+    uint8_t *o = out96 + q * 96;
+    if (st == PT_OK) {
+        from_mont(x, x);
+        from_mont(y, y);
+        store_be48_raw(o, x, 0);
+        store_be48_raw(o + 48, y, 0);
+    } else {
+        for (int i = 0; i < 96; ++i) o[i] = 0;
+        if (st == PT_INF) o[0] = 0x40;
+    }
+    status[q] = (uint8_t)st;
+}
+
+// The same for G2: out192 + 192 q gets x.c1 || x.c0 || y.c1 || y.c0.
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void g2_decompress_kernel(
+    const uint8_t *__restrict__ g2c, size_t count, uint8_t *__restrict__ out192,
+    uint8_t *__restrict__ status) {
+    const size_t q = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (q >= count) return;
+    Fp2 x, y;
+    const int st = decompress_g2(g2c + q * 96, x, y);
+    uint8_t *o = out192 + q * 192;
+    if (st == PT_OK) {
+        from_mont(x.c0, x.c0);
+        from_mont(x.c1, x.c1);
+        from_mont(y.c0, y.c0);
+        from_mont(y.c1, y.c1);
+        store_be48_raw(o, x.c1, 0);
+        store_be48_raw(o + 48, x.c0, 0);
+        store_be48_raw(o + 96, y.c1, 0);
+        store_be48_raw(o + 144, y.c0, 0);
+    } else {
+        for (int i = 0; i < 192; ++i) o[i] = 0;
+        if (st == PT_INF) o[0] = 0x40;
+    }
+    status[q] = (uint8_t)st;
+}
+
 // The crate's final exponentiation (Bls12::final_exponentiation): easy part
 // f^((p^6 - 1)(p^2 + 1)), then the hard-part chain.
 DEV void final_exp(Fp12 &out, const Fp12 &f) {
@@ -2425,6 +2659,42 @@ hipError_t launch_g2_reduce_encode(const uint32_t *ws, const uint8_t *pst, const
     const unsigned blocks = (unsigned)((groups + kPairBlock - 1) / kPairBlock);
     hipLaunchKernelGGL(g2_reduce_encode_kernel, dim3(blocks), dim3(kPairBlock), 0, s, ws, pst,
                        offsets, groups, total, lst, out192, out96, parity, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_g1_prepare_compressed(const uint8_t *g1c, size_t count, uint32_t *keys,
+                                        uint8_t *kst, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g1_prepare_compressed_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g1c,
+                       count, keys, kst);
+    return hipGetLastError();
+}
+
+hipError_t launch_g2_points_compressed(const uint8_t *g2c, size_t count, uint32_t *tab,
+                                       uint8_t *gst, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g2_points_compressed_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g2c,
+                       count, tab, gst);
+    return hipGetLastError();
+}
+
+hipError_t launch_g1_decompress(const uint8_t *g1c, size_t count, uint8_t *out96, uint8_t *status,
+                                hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g1_decompress_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g1c, count,
+                       out96, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_g2_decompress(const uint8_t *g2c, size_t count, uint8_t *out192,
+                                uint8_t *status, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g2_decompress_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g2c, count,
+                       out192, status);
     return hipGetLastError();
 }
 

@@ -37,8 +37,13 @@ the two steps on device tables, `threshold_sign_grouped` the whole for many
 coins.  H = hash_g2(doc) stays with the caller and arrives as a G2 point.
 
 Points are the crate's uncompressed encodings (G1: 96 bytes, G2: 192 bytes,
-big-endian; see include/hbrbc.h).  There is no CPU fallback: without the
-library or a GPU the calls raise `HbrbcUnavailable`.
+big-endian; see include/hbrbc.h) or, as hbbft's messages carry them, the
+compressed ones (48 / 96 bytes): `g1_prepare_compressed` and
+`g2_points_prepare_compressed` build the same tables from those,
+`g1_decompress` / `g2_decompress` turn them into the uncompressed form, and
+`decrypt_shares_grouped_wire` / `threshold_sign_grouped_wire` are the grouped
+functions with every received point in wire form.  There is no CPU fallback:
+without the library or a GPU the calls raise `HbrbcUnavailable`.
 """
 import ctypes
 
@@ -164,6 +169,46 @@ def g1_prepare(g1, stream=None):
     return keys
 
 
+def g1_prepare_compressed(g1c, stream=None):
+    """g1_prepare for compressed points (uint8 [n, 48], the wire form of a
+    DecryptionShare or a PublicKeyShare): the same table, bit for bit."""
+    torch = _torch()
+    n = g1c.shape[0]
+    assert g1c.shape == (n, G1_COMPRESSED_BYTES) and g1c.is_contiguous()
+    keys = torch.empty(max(1, lib().hbrbc_g1_prepared_size(n)), dtype=torch.uint8,
+                       device=g1c.device)
+    _check(lib().hbrbc_g1_prepare_compressed(g1c.data_ptr(), n, keys.data_ptr(),
+                                             _stream(g1c.device, stream)))
+    return keys
+
+
+def g1_decompress(g1c, stream=None):
+    """Compressed G1 points (uint8 [n, 48]) to the uncompressed encoding.
+    Returns (uint8 [n, 96], status uint8 [n]: 0 ok, 1 infinity, 2 invalid); an
+    invalid point gives zero bytes, which every entry rejects."""
+    torch = _torch()
+    n = g1c.shape[0]
+    assert g1c.shape == (n, G1_COMPRESSED_BYTES) and g1c.is_contiguous()
+    out = torch.empty((n, G1_BYTES), dtype=torch.uint8, device=g1c.device)
+    st = torch.empty((n,), dtype=torch.uint8, device=g1c.device)
+    _check(lib().hbrbc_g1_decompress(g1c.data_ptr(), n, out.data_ptr(), st.data_ptr(),
+                                     _stream(g1c.device, stream)))
+    return out, st
+
+
+def g2_decompress(g2c, stream=None):
+    """Compressed G2 points (uint8 [n, 96]) to the uncompressed encoding.
+    Returns (uint8 [n, 192], status uint8 [n]) as g1_decompress."""
+    torch = _torch()
+    n = g2c.shape[0]
+    assert g2c.shape == (n, G2_COMPRESSED_BYTES) and g2c.is_contiguous()
+    out = torch.empty((n, G2_BYTES), dtype=torch.uint8, device=g2c.device)
+    st = torch.empty((n,), dtype=torch.uint8, device=g2c.device)
+    _check(lib().hbrbc_g2_decompress(g2c.data_ptr(), n, out.data_ptr(), st.data_ptr(),
+                                     _stream(g2c.device, stream)))
+    return out, st
+
+
 def pairing_check_prepared_keys(shares, keys, key_points, idx_c, prep, points, idx_b, idx_d,
                                 ws=None, stream=None):
     """count checks e(a_i, P[idx_b[i]]) == e(K[idx_c[i]], P[idx_d[i]]): shares
@@ -225,23 +270,34 @@ def verify_decryption_shares_grouped(ciphertexts, shares, device=0):
     return out
 
 
-def _verify_grouped(ciphertexts, shares, device):
+def _verify_grouped(ciphertexts, shares, device, wire=False):
     """The work of verify_decryption_shares_grouped: returns (outcomes by
     table row, the input position of each row, the g1_prepare table of the
-    shares -- row r holds share order[r])."""
+    shares -- row r holds share order[r]).  `wire`: W, the shares and the key
+    shares arrive compressed (H stays a point)."""
     import numpy as np
     torch = _torch()
     dev = "cuda:%d" % device
-    g2 = np.empty((2 * len(ciphertexts), G2_BYTES), np.uint8)
-    for j, (h, w) in enumerate(ciphertexts):
-        g2[2 * j] = np.frombuffer(h, np.uint8)
-        g2[2 * j + 1] = np.frombuffer(w, np.uint8)
+    g1_width = G1_COMPRESSED_BYTES if wire else G1_BYTES
+    g1_table = g1_prepare_compressed if wire else g1_prepare
+    if wire:
+        # W decompressed on the device (an invalid one becomes zero bytes,
+        # which g2_prepare rejects), then interleaved with H: H_0, W_0, ...
+        dw, _ = g2_decompress(_g2_rows([w for _, w in ciphertexts], dev, G2_COMPRESSED_BYTES))
+        d2 = torch.stack([_g2_rows([h for h, _ in ciphertexts], dev), dw], dim=1)
+        d2 = d2.reshape(2 * len(ciphertexts), G2_BYTES)
+    else:
+        g2 = np.empty((2 * len(ciphertexts), G2_BYTES), np.uint8)
+        for j, (h, w) in enumerate(ciphertexts):
+            g2[2 * j] = np.frombuffer(h, np.uint8)
+            g2[2 * j + 1] = np.frombuffer(w, np.uint8)
+        d2 = torch.from_numpy(g2).to(dev)
     key_ids = {}
     for _, _, pk in shares:
         key_ids.setdefault(bytes(pk), len(key_ids))
     kt = np.stack([np.frombuffer(k, np.uint8) for k in key_ids])
     order = sorted(range(len(shares)), key=lambda i: shares[i][0])
-    g1 = np.empty((len(shares), G1_BYTES), np.uint8)
+    g1 = np.empty((len(shares), g1_width), np.uint8)
     ib = np.empty(len(shares), np.int32)
     ic = np.empty(len(shares), np.int32)
     for r, i in enumerate(order):
@@ -249,7 +305,7 @@ def _verify_grouped(ciphertexts, shares, device):
         g1[r] = np.frombuffer(share, np.uint8)
         ib[r] = 2 * ct
         ic[r] = key_ids[bytes(pk)]
-    d2, dk, d1 = (torch.from_numpy(x).to(dev) for x in (g2, kt, g1))
+    dk, d1 = (torch.from_numpy(x).to(dev) for x in (kt, g1))
     # the three preparations are independent: the G2 points and the key
     # shares are latency-bound chains on few waves, the received shares fill
     # the chip -- each on a stream of its own, the checks wait for all three
@@ -260,9 +316,9 @@ def _verify_grouped(ciphertexts, shares, device):
     with torch.cuda.stream(sides[0]):
         prep = g2_prepare(d2)
     with torch.cuda.stream(sides[1]):
-        ktab = g1_prepare(dk)
+        ktab = g1_table(dk)
     with torch.cuda.stream(sides[2]):
-        sprep = g1_prepare(d1)
+        sprep = g1_table(d1)
     for s_ in sides:
         cur.wait_stream(s_)
     for t_, s_ in ((d2, sides[0]), (dk, sides[1]), (d1, sides[2])):
@@ -431,13 +487,38 @@ def decrypt_shares_grouped(ciphertexts, shares, threshold, device=0):
     ThresholdDecrypt's share map; a node counts once) straight from the
     prepared table.  Returns (bools in the order of `shares`, per ciphertext
     (g96, g48) or None with fewer than threshold + 1 valid shares)."""
+    return _decrypt_shares(ciphertexts, shares, threshold, device, False)
+
+
+def decrypt_shares_grouped_wire(ciphertexts, shares, threshold, device=0):
+    """decrypt_shares_grouped on messages as they arrive: ciphertexts = [(hash
+    G2 uncompressed -- the host computes it as a point --, W G2 compressed, 96
+    bytes)], shares = [(ciphertext index, node index, share G1 compressed, 48
+    bytes, pk_share G1 compressed, 48 bytes)].  The points are decompressed on
+    the device (the square roots, sign choices and order-r checks of
+    `into_affine`); a point that does not decode fails its checks.  Returns
+    what decrypt_shares_grouped returns."""
+    for _, w in ciphertexts:
+        if len(w) != G2_COMPRESSED_BYTES:
+            raise ValueError("W of %d bytes, expected %d" % (len(w), G2_COMPRESSED_BYTES))
+    for _, _, share, pk in shares:
+        for x in (share, pk):
+            if len(x) != G1_COMPRESSED_BYTES:
+                raise ValueError("G1 encoding of %d bytes, expected %d"
+                                 % (len(x), G1_COMPRESSED_BYTES))
+    _need_gpu()
+    return _decrypt_shares(ciphertexts, shares, threshold, device, True)
+
+
+def _decrypt_shares(ciphertexts, shares, threshold, device, wire):
+    """The body of decrypt_shares_grouped and its wire twin."""
     import numpy as np
     torch = _torch()
     outs = [None] * len(ciphertexts)
     if not shares:
         return [], outs
     okh, order, sprep = _verify_grouped(ciphertexts, [(c, s, pk) for c, _, s, pk in shares],
-                                        device)
+                                        device, wire)
     flags = [False] * len(shares)
     valid = [[] for _ in ciphertexts]   # per ciphertext: (node index, table row)
     for r, i in enumerate(order):
@@ -480,6 +561,18 @@ def g2_points_prepare(g2, stream=None):
     tab = torch.empty(lib().hbrbc_g2_points_size(n), dtype=torch.uint8, device=g2.device)
     _check(lib().hbrbc_g2_points_prepare(g2.data_ptr(), n, tab.data_ptr(),
                                          _stream(g2.device, stream)))
+    return tab
+
+
+def g2_points_prepare_compressed(g2c, stream=None):
+    """g2_points_prepare for compressed points (uint8 [n, 96], the wire form
+    of a SignatureShare): the same table, bit for bit."""
+    torch = _torch()
+    n = g2c.shape[0]
+    assert g2c.shape == (n, G2_COMPRESSED_BYTES) and g2c.is_contiguous()
+    tab = torch.empty(lib().hbrbc_g2_points_size(n), dtype=torch.uint8, device=g2c.device)
+    _check(lib().hbrbc_g2_points_prepare_compressed(g2c.data_ptr(), n, tab.data_ptr(),
+                                                    _stream(g2c.device, stream)))
     return tab
 
 
@@ -584,23 +677,23 @@ def _need_gpu():
         raise HbrbcUnavailable("no HIP device visible")
 
 
-def _g2_rows(points, dev):
+def _g2_rows(points, dev, width=G2_BYTES):
     import numpy as np
     for p in points:
-        if len(p) != G2_BYTES:
-            raise ValueError("G2 encoding of %d bytes, expected %d" % (len(p), G2_BYTES))
-    a = np.empty((len(points), G2_BYTES), np.uint8)
+        if len(p) != width:
+            raise ValueError("G2 encoding of %d bytes, expected %d" % (len(p), width))
+    a = np.empty((len(points), width), np.uint8)
     for r, p in enumerate(points):
         a[r] = np.frombuffer(p, np.uint8)
     return _torch().from_numpy(a).to(dev)
 
 
-def _g1_rows(points, dev):
+def _g1_rows(points, dev, width=G1_BYTES):
     import numpy as np
     for p in points:
-        if len(p) != G1_BYTES:
-            raise ValueError("G1 encoding of %d bytes, expected %d" % (len(p), G1_BYTES))
-    a = np.empty((len(points), G1_BYTES), np.uint8)
+        if len(p) != width:
+            raise ValueError("G1 encoding of %d bytes, expected %d" % (len(p), width))
+    a = np.empty((len(points), width), np.uint8)
     for r, p in enumerate(points):
         a[r] = np.frombuffer(p, np.uint8)
     return _torch().from_numpy(a).to(dev)
@@ -685,10 +778,29 @@ def threshold_sign_grouped(documents, shares, threshold, public_key, device=0):
     `public_key` through the same check kernel.  Returns (bools in the order of
     `shares`, per document (sig192, sig96, parity, verified) or None with fewer
     than threshold + 1 valid shares)."""
+    return _threshold_sign(documents, shares, threshold, public_key, device, False)
+
+
+def threshold_sign_grouped_wire(documents, shares, threshold, public_key, device=0):
+    """threshold_sign_grouped on messages as they arrive: documents = [hash G2
+    uncompressed -- the host computes it as a point], shares = [(document
+    index, node index, share G2 compressed, 96 bytes, pk_share G1 compressed,
+    48 bytes)], public_key G1 compressed, 48 bytes.  The points are
+    decompressed on the device; a point that does not decode fails its checks.
+    Returns what threshold_sign_grouped returns."""
+    return _threshold_sign(documents, shares, threshold, public_key, device, True)
+
+
+def _threshold_sign(documents, shares, threshold, public_key, device, wire):
+    """The body of threshold_sign_grouped and its wire twin."""
     import numpy as np
     torch = _torch()
-    if len(public_key) != G1_BYTES:
-        raise ValueError("public key of %d bytes, expected %d" % (len(public_key), G1_BYTES))
+    g1_width = G1_COMPRESSED_BYTES if wire else G1_BYTES
+    g2_width = G2_COMPRESSED_BYTES if wire else G2_BYTES
+    g1_table = g1_prepare_compressed if wire else g1_prepare
+    g2_table = g2_points_prepare_compressed if wire else g2_points_prepare
+    if len(public_key) != g1_width:
+        raise ValueError("public key of %d bytes, expected %d" % (len(public_key), g1_width))
     _need_gpu()
     outs = [None] * len(documents)
     if not shares:
@@ -698,8 +810,8 @@ def threshold_sign_grouped(documents, shares, threshold, public_key, device=0):
     keys, ik = _dedup([public_key] + [pk for _, _, _, pk in shares])
     order = sorted(range(len(shares)), key=lambda i: shares[i][0])
     d2 = _g2_rows(documents, dev)
-    dk = _g1_rows(keys, dev)
-    ds = _g2_rows([shares[i][2] for i in order], dev)
+    dk = _g1_rows(keys, dev, g1_width)
+    ds = _g2_rows([shares[i][2] for i in order], dev, g2_width)
     ih = np.asarray([shares[i][0] for i in order], np.int32)
     ic = np.asarray([ik[1 + i] for i in order], np.int32)
     # three independent preparations, each on a stream of its own (see
@@ -711,9 +823,9 @@ def threshold_sign_grouped(documents, shares, threshold, public_key, device=0):
     with torch.cuda.stream(sides[0]):
         prep = g2_prepare(d2)
     with torch.cuda.stream(sides[1]):
-        ktab = g1_prepare(dk)
+        ktab = g1_table(dk)
     with torch.cuda.stream(sides[2]):
-        stab = g2_points_prepare(ds)
+        stab = g2_table(ds)
     for s_ in sides:
         cur.wait_stream(s_)
     for t_, s_ in ((d2, sides[0]), (dk, sides[1]), (ds, sides[2])):

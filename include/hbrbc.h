@@ -563,7 +563,8 @@ int hbrbc_decrypt_combine(const uint8_t *shares, const uint32_t *idx, size_t n, 
  * in G2 -- and checks the result against the master public key (:249-270) in
  * the same form.  hash_g2 (a ChaCha-seeded G2 sample) stays with the caller,
  * like hash_g1_g2: H arrives as a G2 point.  Shares arrive in the uncompressed
- * encoding (192 bytes); decompressing 96-byte wire shares is the caller's.
+ * encoding (192 bytes) here, or as 96-byte wire shares through
+ * hbrbc_g2_points_prepare_compressed below.
  *
  * The G2 point on the right of the check differs per share, so it is not a
  * prepared-lines point: the shares are decoded and checked once (canonical
@@ -617,6 +618,34 @@ int hbrbc_sig_combine_prepared(const void *sig_table, size_t sig_count, const in
  * encodings. */
 int hbrbc_sig_combine(const uint8_t *shares, const uint32_t *idx, size_t n, uint8_t out192[192],
                       uint8_t out96[96], uint8_t *parity);
+
+/* ---- compressed wire encodings -------------------------------------------
+ * hbbft's messages carry points in the crate's compressed form: 48 bytes for
+ * G1 (DecryptionShare, PublicKeyShare, a ciphertext's U: x big-endian), 96 for
+ * G2 (SignatureShare, a ciphertext's W: x.c1 || x.c0), with three flags in
+ * byte 0: 0x80 compressed (must be set), 0x40 infinity (every other bit then
+ * zero), 0x20 y is the larger of y and -y (as integers; in Fp2 c1 compared
+ * first and c0 only when the c1 are equal).  The entries below decode as
+ * G1Compressed::into_affine / G2Compressed::into_affine do: flags, x < p,
+ * y = sqrt(x^3 + b) (no root: invalid) with the sign the flag names, order r.
+ * Device memory, async on `stream`.
+ *
+ * hbrbc_g1_prepare / hbrbc_g2_points_prepare from compressed input: g1c holds
+ * count x 48 bytes, g2c count x 96; the tables (hbrbc_g1_prepared_size /
+ * hbrbc_g2_points_size bytes) are those of the uncompressed entries, bit for
+ * bit, and every entry that takes such a table takes these. */
+int hbrbc_g1_prepare_compressed(const uint8_t *g1c, size_t count, void *prepared, void *stream);
+int hbrbc_g2_points_prepare_compressed(const uint8_t *g2c, size_t count, void *table,
+                                       void *stream);
+/* Compressed to uncompressed: out96 + 96 i (out192 + 192 i) receives point i
+ * in the encoding the other entries take -- zero bytes for an invalid point,
+ * 0x40 and zeros for infinity -- and status[i] 0 ok, 1 infinity, 2 invalid.
+ * A ciphertext's W reaches hbrbc_g2_prepare this way, its U the pairing
+ * checks. */
+int hbrbc_g1_decompress(const uint8_t *g1c, size_t count, uint8_t *out96, uint8_t *status,
+                        void *stream);
+int hbrbc_g2_decompress(const uint8_t *g2c, size_t count, uint8_t *out192, uint8_t *status,
+                        void *stream);
 
 /* ---- the Broadcast state machine, batched --------------- */
 /* Many instances x nodes of `Broadcast` (broadcast.rs:228-558) in synchronous
