@@ -170,6 +170,9 @@ def lib():
         "hbrbc_g2_points_prepare_compressed": (ctypes.c_int, [_P, _S, _P, _P]),
         "hbrbc_g1_decompress": (ctypes.c_int, [_P, _S, _P, _P, _P]),
         "hbrbc_g2_decompress": (ctypes.c_int, [_P, _S, _P, _P, _P]),
+        "hbrbc_g1_poly_eval_prepared": (ctypes.c_int, [_P, _S, _P, _P, _S, _P, _P, _S, _P, _P, _P,
+                                                       _P, _P]),
+        "hbrbc_g1_base_mul_check": (ctypes.c_int, [_P, _S, _P, _P, _S, _P, _P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

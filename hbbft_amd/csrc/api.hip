@@ -2540,6 +2540,39 @@ int hbrbc_decrypt_combine(const uint8_t *shares, const uint32_t *idx, size_t n, 
     return HBRBC_OK;
 }
 
+// ---- key generation (pairing.hip): SyncKeyGen's commitment evaluations ------
+int hbrbc_g1_poly_eval_prepared(const void *a_prepared, size_t prepared_count, const int32_t *rows,
+                                const uint32_t *offsets, size_t polys, const int32_t *poly,
+                                const uint32_t *x, size_t evals, void *out_table, uint8_t *out96,
+                                uint8_t *out48, uint8_t *status_out, void *stream) {
+    if (evals == 0) return HBRBC_OK;
+    if (!a_prepared || !rows || !offsets || !poly || !x || !out_table || !status_out)
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    const uint32_t *tab = static_cast<const uint32_t *>(a_prepared);
+    const uint8_t *tst =
+        static_cast<const uint8_t *>(a_prepared) + round_up(g1_key_words(prepared_count) * 4, 256);
+    uint32_t *otab = static_cast<uint32_t *>(out_table);
+    uint8_t *ost = static_cast<uint8_t *>(out_table) + round_up(g1_key_words(evals) * 4, 256);
+    HB_HIP(launch_g1_horner(tab, tst, prepared_count, rows, offsets, polys, poly, x, evals, otab,
+                            ost, out96, out48, status_out, static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
+int hbrbc_g1_base_mul_check(const void *a_prepared, size_t prepared_count, const int32_t *rows,
+                            const uint8_t *scalars, size_t count, uint8_t *ok_out, void *stream) {
+    if (count == 0) return HBRBC_OK;
+    if (!a_prepared || !rows || !scalars || !ok_out)
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    const uint32_t *tab = static_cast<const uint32_t *>(a_prepared);
+    const uint8_t *tst =
+        static_cast<const uint8_t *>(a_prepared) + round_up(g1_key_words(prepared_count) * 4, 256);
+    HB_HIP(launch_g1_base_mul_check(tab, tst, prepared_count, rows, scalars, count, ok_out,
+                                    static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
 // ---- threshold signatures (pairing.hip): ThresholdSign, the coin ----------
 size_t hbrbc_g2_points_size(size_t points) {
     return round_up(g2_point_table_words(points) * 4, 256) + round_up(points, 256);

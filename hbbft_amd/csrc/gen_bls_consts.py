@@ -29,6 +29,10 @@ square a the power t = a^((p-3)/4) is 1/sqrt(a) and t a the root; kSqrtExp is
 that exponent as plain limbs (fp_pow_sqrt walks it in 4-bit windows, top
 window first, which main() asserts to be non-zero) and kHalf = 1/2, for the
 (a0 + |a|)/2 of the square root in Fp2 by norms.
+
+Key generation (g1_base_mul_check_kernel): the three operands of the GLV loop
+for the fixed base G1::one() -- the generator, Q = [x^2] G1::one() and their
+sum -- as affine constants.
 """
 P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
 X_ABS = 0xd201000000010000
@@ -107,6 +111,35 @@ def gamma_g2():
     return gamma
 
 
+def g1_add(a, b):
+    """Affine addition on y^2 = x^3 + 4 (None = infinity)."""
+    if a is None or b is None:
+        return b if a is None else a
+    if a[0] == b[0]:
+        if (a[1] + b[1]) % P == 0:
+            return None
+        lam = 3 * a[0] * a[0] * pow(2 * a[1], P - 2, P) % P
+    else:
+        lam = (b[1] - a[1]) * pow(b[0] - a[0], P - 2, P) % P
+    x = (lam * lam - a[0] - b[0]) % P
+    return (x, (lam * (a[0] - x) - a[1]) % P)
+
+
+def g1_gen_glv():
+    """Q = [x^2] G1::one() = (beta x, -y) and G1::one() + Q, the operands of
+    the fixed-base GLV loop (g1_base_mul_check_kernel); Q is asserted against
+    plain double-and-add."""
+    g, acc, pt, k = (G1_X, G1_Y), None, (G1_X, G1_Y), X_ABS * X_ABS
+    while k:
+        if k & 1:
+            acc = g1_add(acc, pt)
+        pt = g1_add(pt, pt)
+        k >>= 1
+    q = (beta_g1() * G1_X % P, P - G1_Y)
+    assert acc == q, "Q = [x^2] G"
+    return q, g1_add(g, q)
+
+
 def arr(name, v):
     return "constexpr uint32_t %s[12] = {%s};" % (name, ", ".join("0x%08xu" % x for x in limbs(v)))
 
@@ -130,6 +163,7 @@ def main():
     assert P % 4 == 3 and SQRT_EXP >> (4 * (SQRT_WINDOWS - 1)) != 0
     assert pow(9, SQRT_EXP, P) * 3 % P in (1, P - 1)   # 1/sqrt(9) = +-1/3
     inv29 = (-pow(P, -1, 1 << 29)) % (1 << 29)
+    gen_q, gen_t = g1_gen_glv()
     out = [
         "// Generated by gen_bls_consts.py -- BLS12-381 constants for pairing.hip.",
         "// Limbs little-endian (32-bit); field elements in Montgomery form, R = 2^406.",
@@ -165,6 +199,10 @@ def main():
         arr("kSqrtExp", SQRT_EXP) + "  // (p - 3) / 4, plain: a^this = 1/sqrt(a)",
         "constexpr int kSqrtExpWindows = %d;  // 4-bit windows of kSqrtExp" % SQRT_WINDOWS,
         arr("kHalf", mont((P + 1) // 2)) + "  // 1/2",
+        arr("kG1GenY", mont(G1_Y)) + "  // G1::one(), affine y",
+        arr("kG1GenQX", mont(gen_q[0])) + "  // Q = [x^2] G1::one() = (beta x, -y): x (y is kG1GenNegY)",
+        arr("kG1GenTX", mont(gen_t[0])) + "  // G1::one() + Q, affine x",
+        arr("kG1GenTY", mont(gen_t[1])) + "  // G1::one() + Q, affine y",
         "}}  // namespace hbrbc::bls",
     ]
     print("\n".join(out))

@@ -281,6 +281,17 @@ hipError_t launch_g1_scalar_mul(const uint32_t *tab, const uint8_t *tst, size_t 
 hipError_t launch_g1_reduce_encode(const uint32_t *ws, const uint8_t *pst, const uint32_t *offsets,
                                    size_t groups, size_t total, const uint8_t *lst, uint8_t *out96,
                                    uint8_t *out48, uint8_t *status, hipStream_t s);
+// key generation (pairing.hip): ragged G1 polynomials over a g1_prepare table
+// evaluated at small integers (Horner), results in table form (otab, ost) and
+// optionally encoded; fixed-base checks [s] G1::one() == T[row]
+hipError_t launch_g1_horner(const uint32_t *tab, const uint8_t *tst, size_t nprep,
+                            const int32_t *rows, const uint32_t *offsets, size_t polys,
+                            const int32_t *poly, const uint32_t *x, size_t evals, uint32_t *otab,
+                            uint8_t *ost, uint8_t *out96, uint8_t *out48, uint8_t *status,
+                            hipStream_t s);
+hipError_t launch_g1_base_mul_check(const uint32_t *tab, const uint8_t *tst, size_t nprep,
+                                    const int32_t *rows, const uint8_t *scalars, size_t count,
+                                    uint8_t *ok, hipStream_t s);
 // threshold signatures (pairing.hip): decoded G2 points (a table of
 // g2_point_table_words(points) words), the share check e(K, P) == e(G1::one(),
 // S) with S from that table, [k] Q per share into a limb-major workspace of

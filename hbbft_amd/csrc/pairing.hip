@@ -1713,6 +1713,40 @@ DEV void store_be48_raw(uint8_t *dst, const Fp &c, uint8_t flags) {
     dst[0] |= flags;
 }
 
+// A projective result to affine with one inversion: (xm, ym) Montgomery
+// (zero for infinity) and, where the pointers are non-null, the two encodings
+// described below into buffers the caller has zeroed.  Returns CB_OK or CB_INF.
+DEV int g1_affine_encode(const PtProj<Fp> &acc, Fp &xm, Fp &ym, uint8_t *o96, uint8_t *o48) {
+    if (fp_is_zero(acc.z)) {
+        fp_zero(xm);
+        fp_zero(ym);
+        if (o96) o96[0] = 0x40;
+        if (o48) o48[0] = 0xC0;
+        return CB_INF;
+    }
+    Fp zi, x, y, ny;
+    fp_inv(zi, acc.z);
+    fp_mul(xm, acc.x, zi);
+    fp_mul(ym, acc.y, zi);
+    if (!o96 && !o48) return CB_OK;
+    from_mont(x, xm);
+    from_mont(y, ym);
+    // p - y against y, most significant limb first
+    uint32_t br = 0;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) ny.l[i] = subb(kP[i], y.l[i], br, &br);
+    int cmp = 0;   // sign of y - (p - y)
+#pragma unroll
+    for (int i = NL - 1; i >= 0; --i)
+        if (cmp == 0 && y.l[i] != ny.l[i]) cmp = y.l[i] > ny.l[i] ? 1 : -1;
+    if (o96) {
+        store_be48_raw(o96, x, 0);
+        store_be48_raw(o96 + 48, y, 0);
+    }
+    if (o48) store_be48_raw(o48, x, (uint8_t)(0x80 | (cmp > 0 ? 0x20 : 0)));
+    return CB_OK;
+}
+
 // Kernel: one lane per group.  Sums the group's projective points, converts
 // to affine with one inversion and writes the uncompressed encoding (96
 // bytes, x || y) and the compressed one (48 bytes: x with 0x80 set, 0x20 set
@@ -1744,31 +1778,155 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G
             load_pt(q, ws, total, k);
             pt_add_proj(acc, q);
         }
-        if (fp_is_zero(acc.z)) {
-            st = CB_INF;
-            o96[0] = 0x40;
-            o48[0] = 0xC0;
-        } else {
-            Fp zi, x, y, ny;
-            fp_inv(zi, acc.z);
-            fp_mul(x, acc.x, zi);
-            fp_mul(y, acc.y, zi);
-            from_mont(x, x);
-            from_mont(y, y);
-            // p - y against y, most significant limb first
-            uint32_t br = 0;
-#pragma unroll
-            for (int i = 0; i < NL; ++i) ny.l[i] = subb(kP[i], y.l[i], br, &br);
-            int cmp = 0;   // sign of y - (p - y)
-#pragma unroll
-            for (int i = NL - 1; i >= 0; --i)
-                if (cmp == 0 && y.l[i] != ny.l[i]) cmp = y.l[i] > ny.l[i] ? 1 : -1;
-            store_be48_raw(o96, x, 0);
-            store_be48_raw(o96 + 48, y, 0);
-            store_be48_raw(o48, x, (uint8_t)(0x80 | (cmp > 0 ? 0x20 : 0)));
-        }
+        Fp xm, ym;
+        st = g1_affine_encode(acc, xm, ym, o96, o48);
     }
     status[g] = (uint8_t)st;
+}
+
+// ------------------------------------------------------------ key generation
+// SyncKeyGen (sync_key_gen.rs) evaluates G1 commitments at node indices:
+// `commit.row(our_idx + 1)` per Part (:557), `commit.evaluate(our_idx + 1,
+// sender_idx + 1)` per Ack (:603), `commit.row(0)` summed in `generate`
+// (:516-534), and `PublicKeySet::public_key_share(i)` = `commit.evaluate(i +
+// 1)` for the key shares every share check reads.  The evaluation points are
+// integers of a few bits, so Horner's rule needs bits(x) doublings per
+// coefficient where a linear combination with scalars x^k mod r pays a
+// 128-step GLV multiplication per term.
+//
+// Kernel: one lane per evaluation e of polynomial poly[e] at x[e] (the raw
+// point: the crate's IntoFr of an integer, not index + 1).  Polynomial p has
+// the coefficients T[rows[offsets[p] .. offsets[p + 1])] of a g1_prepare
+// table, constant term first; degrees are ragged and the row count is
+// offsets[polys], to which every range is clamped.  From acc = identity, for
+// k from the top coefficient down: acc = [x] acc (left-to-right double-and-
+// add over the 32 - clz(x) significant bits on a copy of acc, which stands
+// for the leading one: complete formulas, no special cases -- no bits give
+// the identity, so x = 0 yields C_0, and x = 1 the plain sum), then acc +=
+// C_k by the mixed addition (a coefficient at infinity is skipped).  Loop bounds are per lane: lanes of a wave may differ in degree
+// and bit length.  An invalid coefficient, a row outside the table or a poly
+// outside [0, polys) gives status 2.
+// The result goes out in g1_prepare table form (Montgomery affine x || y,
+// zero unless the status is 0; status byte 0 ok, 1 infinity, 2 invalid), so
+// it serves as the table of a second evaluation or of the check below, and,
+// where out96 / out48 are non-null, in the encodings of the combine.
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_horner_kernel(
+    const uint32_t *__restrict__ tab, const uint8_t *__restrict__ tst, size_t nprep,
+    const int32_t *__restrict__ rows, const uint32_t *__restrict__ offsets, size_t polys,
+    const int32_t *__restrict__ poly, const uint32_t *__restrict__ xs, size_t evals,
+    uint32_t *__restrict__ otab, uint8_t *__restrict__ ost, uint8_t *__restrict__ out96,
+    uint8_t *__restrict__ out48, uint8_t *__restrict__ status) {
+    const size_t e = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (e >= evals) return;
+    const int32_t p = poly[e];
+    const uint32_t xv = xs[e];
+    const int nbits = xv ? 32 - __builtin_clz(xv) : 0;
+    int st = PT_OK;
+    size_t b = 0, en = 0;
+    if (p >= 0 && (size_t)p < polys)
+        group_range(offsets, (size_t)p, offsets[polys], b, en);
+    else
+        st = PT_BAD;
+    PtProj<Fp> acc;
+    pt_identity(acc);
+    for (size_t k = en; k > b && st == PT_OK; --k) {
+        if (k != en) {   // [x] acc; the top coefficient starts from the identity
+            PtProj<Fp> t = acc;   // the leading one of x
+            if (nbits == 0) pt_identity(t);
+            for (int bit = nbits - 2; bit >= 0; --bit) {
+                pt_dbl(t);
+                if ((xv >> bit) & 1u) pt_add_proj(t, acc);
+            }
+            acc = t;
+        }
+        const int32_t row = rows[k - 1];
+        const int cst = (row >= 0 && (size_t)row < nprep) ? tst[row] : PT_BAD;
+        if (cst == PT_OK) {
+            Fp cx, cy;
+            load_g1_key(tab + (size_t)row * kG1KeyWords, cx, cy);
+            pt_add_affine(acc, cx, cy);
+        } else if (cst != PT_INF) {
+            st = PT_BAD;
+        }
+    }
+    uint8_t *o96 = out96 ? out96 + 96 * e : nullptr, *o48 = out48 ? out48 + 48 * e : nullptr;
+    if (o96)
+        for (int i = 0; i < 96; ++i) o96[i] = 0;
+    if (o48)
+        for (int i = 0; i < 48; ++i) o48[i] = 0;
+    Fp xm, ym;
+    if (st == PT_OK) {
+        st = g1_affine_encode(acc, xm, ym, o96, o48);   // CB_OK / CB_INF = PT_OK / PT_INF
+    } else {
+        fp_zero(xm);
+        fp_zero(ym);
+    }
+    uint32_t *dst = otab + e * kG1KeyWords;
+#pragma unroll
+    for (int w = 0; w < NL; w += 4) {
+        *reinterpret_cast<uint4 *>(dst + w) = make_uint4(xm.l[w], xm.l[w + 1], xm.l[w + 2], xm.l[w + 3]);
+        *reinterpret_cast<uint4 *>(dst + NL + w) = make_uint4(ym.l[w], ym.l[w + 1], ym.l[w + 2], ym.l[w + 3]);
+    }
+    ost[e] = (uint8_t)st;
+    status[e] = (uint8_t)st;
+}
+
+// Kernel: one lane per check [s_i] G1::one() == T[rows[i]] -- the
+// `row.commitment() != commit_row` of a Part (sync_key_gen.rs:569, one check
+// per coefficient) and the `G1Affine::one().mul(val)` of an Ack (:603).  s is
+// 32 big-endian bytes; the multiplication is the GLV loop of
+// g1_scalar_mul_kernel with P = G1::one(), Q = [x^2] P and P + Q as affine
+// constants (the mixed addition with a selected operand), the comparison
+// projective against affine: X == x Z, Y == y Z, Z != 0; a table entry at
+// infinity equals a result at infinity.  ok: 1 equal, 0 not, 2 for an invalid
+// table entry, a row outside the table or s >= r.
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_base_mul_check_kernel(
+    const uint32_t *__restrict__ tab, const uint8_t *__restrict__ tst, size_t nprep,
+    const int32_t *__restrict__ rows, const uint8_t *__restrict__ scalars, size_t count,
+    uint8_t *__restrict__ ok) {
+    const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (i >= count) return;
+    const int32_t row = rows[i];
+    int st = (row >= 0 && (size_t)row < nprep) ? tst[row] : PT_BAD;
+    Fr k;
+    fr_load_be32(k, scalars + 32 * i);
+    if (!fr_is_canonical(k)) st = PT_BAD;
+    if (st == PT_BAD) {
+        ok[i] = 2;
+        return;
+    }
+    uint64_t k1hi, k1lo, k2hi, k2lo;
+    glv_split(k, k1hi, k1lo, k2hi, k2lo);
+    PtProj<Fp> acc;
+    pt_identity(acc);
+    for (int b = 127; b >= 0; --b) {
+        pt_dbl(acc);
+        const unsigned sel = (unsigned)(k1hi >> 63) | ((unsigned)(k2hi >> 63) << 1);
+        k1hi = (k1hi << 1) | (k1lo >> 63);
+        k1lo <<= 1;
+        k2hi = (k2hi << 1) | (k2lo >> 63);
+        k2lo <<= 1;
+        if (sel) {
+            Fp ox, oy;
+#pragma unroll
+            for (int w = 0; w < NL; ++w) {
+                ox.l[w] = sel == 1 ? kG1GenX[w] : (sel == 2 ? kG1GenQX[w] : kG1GenTX[w]);
+                oy.l[w] = sel == 1 ? kG1GenY[w] : (sel == 2 ? kG1GenNegY[w] : kG1GenTY[w]);
+            }
+            pt_add_affine(acc, ox, oy);
+        }
+    }
+    bool eq;
+    if (st == PT_INF) {
+        eq = fp_is_zero(acc.z);
+    } else {
+        Fp x, y, l, r;
+        load_g1_key(tab + (size_t)row * kG1KeyWords, x, y);
+        fp_mul(l, x, acc.z);
+        fp_mul(r, y, acc.z);
+        eq = !fp_is_zero(acc.z) && fp_eq(l, acc.x) && fp_eq(r, acc.y);
+    }
+    ok[i] = eq ? 1 : 0;
 }
 
 // One lane per check e(a, b) == e(c, d) with b, d prepared (points ib[i],
@@ -2614,6 +2772,28 @@ hipError_t launch_g1_reduce_encode(const uint32_t *ws, const uint8_t *pst, const
     const unsigned blocks = (unsigned)((groups + kPairBlock - 1) / kPairBlock);
     hipLaunchKernelGGL(g1_reduce_encode_kernel, dim3(blocks), dim3(kPairBlock), 0, s, ws, pst,
                        offsets, groups, total, lst, out96, out48, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_g1_horner(const uint32_t *tab, const uint8_t *tst, size_t nprep,
+                            const int32_t *rows, const uint32_t *offsets, size_t polys,
+                            const int32_t *poly, const uint32_t *x, size_t evals, uint32_t *otab,
+                            uint8_t *ost, uint8_t *out96, uint8_t *out48, uint8_t *status,
+                            hipStream_t s) {
+    if (evals == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((evals + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g1_horner_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab, tst, nprep,
+                       rows, offsets, polys, poly, x, evals, otab, ost, out96, out48, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_g1_base_mul_check(const uint32_t *tab, const uint8_t *tst, size_t nprep,
+                                    const int32_t *rows, const uint8_t *scalars, size_t count,
+                                    uint8_t *ok, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g1_base_mul_check_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab, tst,
+                       nprep, rows, scalars, count, ok);
     return hipGetLastError();
 }
 

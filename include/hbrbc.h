@@ -553,6 +553,43 @@ int hbrbc_decrypt_combine_prepared(const void *a_prepared, size_t prepared_count
 int hbrbc_decrypt_combine(const uint8_t *shares, const uint32_t *idx, size_t n, uint8_t out96[96],
                           uint8_t out48[48]);
 
+/* ---- key generation: SyncKeyGen's commitment evaluations -----------------
+ * `SyncKeyGen` (sync_key_gen.rs) checks each Part against `commit.row(our_idx
+ * + 1)` (:557, :569) and each Ack against `commit.evaluate(our_idx + 1,
+ * sender_idx + 1)` (:603), `generate` sums `commit.row(0)` over the complete
+ * parts (:516-534), and `PublicKeySet::public_key_share(i)` is
+ * `commit.evaluate(i + 1)`: G1 polynomials evaluated at small integers, and
+ * comparisons with [s] G1::one().  Decrypting rows and values (`xor_with_hash`)
+ * stays with the caller; scalars arrive as Fr.  Device memory, async on
+ * `stream`; neither entry reads anything back.
+ *
+ * Evaluates ragged polynomials over a table T of hbrbc_g1_prepare with
+ * `prepared_count` points: polynomial p has the coefficients
+ * T[rows[offsets[p] .. offsets[p + 1])], constant term first (offsets: polys +
+ * 1 entries, a prefix sum whose last entry is the length of rows; every range
+ * is clamped to it).  Evaluation e is polynomial poly[e] at x[e], the raw
+ * point (the crate's IntoFr of an integer; x = 0 gives the constant term, x =
+ * 1 the sum of the coefficients; an empty polynomial is the identity), by
+ * Horner's rule with double-and-add over the significant bits of x.
+ * status_out[e]: 0 ok, 1 ok and the point at infinity, 2 an invalid table
+ * entry, a row outside the table or poly[e] outside [0, polys).  Results go to
+ * `out_table` (hbrbc_g1_prepared_size(evals) bytes) in the form of
+ * hbrbc_g1_prepare over `evals` points, bit for bit -- every entry that takes
+ * such a table takes it, this one included -- and, where the pointers are
+ * non-null, to out96 + 96 e and out48 + 48 e in the encodings of the combine
+ * above (zero bytes for status 2). */
+int hbrbc_g1_poly_eval_prepared(const void *a_prepared, size_t prepared_count, const int32_t *rows,
+                                const uint32_t *offsets, size_t polys, const int32_t *poly,
+                                const uint32_t *x, size_t evals, void *out_table, uint8_t *out96,
+                                uint8_t *out48, uint8_t *status_out, void *stream);
+/* count checks [s_i] G1::one() == T[rows[i]] over a table T of hbrbc_g1_prepare
+ * (or of the entry above) with `prepared_count` points: scalars + 32 i holds
+ * s_i as 32 big-endian bytes.  ok_out[i]: 1 equal, 0 not, 2 an invalid table
+ * entry, a row outside the table or s_i >= r.  A table entry at infinity
+ * equals [0] G1::one(). */
+int hbrbc_g1_base_mul_check(const void *a_prepared, size_t prepared_count, const int32_t *rows,
+                            const uint8_t *scalars, size_t count, uint8_t *ok_out, void *stream);
+
 /* ---- threshold signatures: ThresholdSign, the coin of BinaryAgreement ----
  * `ThresholdSign` (threshold_sign.rs; binary_agreement.rs:444-446 creates one
  * per coin round and :404 takes `sig.parity()` as the coin) checks every
