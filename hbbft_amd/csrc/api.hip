@@ -2383,7 +2383,32 @@ int hbrbc_pairing_check(const uint8_t a[96], const uint8_t b[192], const uint8_t
     return HBRBC_OK;
 }
 
-// ---- decryption-share combine (pairing.hip): PublicKeySet::decrypt up to g --
+// ---- share combine (pairing.hip): PublicKeySet::decrypt up to g in G1, -------
+// combine_signatures in G2.  The two differ in sizes and launchers only:
+struct CombineGroup {
+    size_t enc;                           // bytes of the uncompressed encoding (compressed: half)
+    size_t (*table_words)(size_t);        // affine table; its status bytes sit behind
+    size_t (*point_words)(size_t);        // projective workspace points
+    int (*prepare)(const uint8_t *, size_t, void *, void *);
+    decltype(&launch_g1_scalar_mul) scalar_mul;
+    decltype(&launch_g2_reduce_encode) reduce_encode;   // G1 writes no parity byte
+    const char *what;
+};
+
+static hipError_t g1_reduce_encode_np(const uint32_t *ws, const uint8_t *pst,
+                                      const uint32_t *offsets, size_t groups, size_t total,
+                                      const uint8_t *lst, uint8_t *out96, uint8_t *out48, uint8_t *,
+                                      uint8_t *status, hipStream_t s) {
+    return launch_g1_reduce_encode(ws, pst, offsets, groups, total, lst, out96, out48, status, s);
+}
+
+static const CombineGroup kCombineG1 = {96, g1_key_words, g1_point_words, hbrbc_g1_prepare,
+                                        launch_g1_scalar_mul, g1_reduce_encode_np,
+                                        "decrypt combine"};
+static const CombineGroup kCombineG2 = {192, g2_point_table_words, g2_point_words,
+                                        hbrbc_g2_points_prepare, launch_g2_scalar_mul,
+                                        launch_g2_reduce_encode, "signature combine"};
+
 // workspace: projective points (limb-major), per-share status, coefficients,
 // per-group Lagrange status
 struct CombineWs {
@@ -2391,18 +2416,30 @@ struct CombineWs {
     uint8_t *pst, *coeffs, *lst;
 };
 
-static CombineWs combine_ws(void *workspace, size_t total, size_t groups) {
+static CombineWs combine_ws(const CombineGroup &G, void *workspace, size_t total) {
     uint8_t *p = static_cast<uint8_t *>(workspace);
     CombineWs w;
     w.pts = reinterpret_cast<uint32_t *>(p);
-    p += round_up(g1_point_words(total) * 4, 256);
+    p += round_up(G.point_words(total) * 4, 256);
     w.pst = p;
     p += round_up(total, 256);
     w.coeffs = p;
     p += round_up(total * 32, 256);
     w.lst = p;
-    (void)groups;
     return w;
+}
+
+static size_t combine_workspace_size(const CombineGroup &G, size_t total_shares, size_t groups) {
+    return round_up(G.point_words(total_shares) * 4, 256) + round_up(total_shares, 256) +
+           round_up(total_shares * 32, 256) + round_up(groups, 256);
+}
+
+size_t hbrbc_g1_combine_workspace_size(size_t total_shares, size_t groups) {
+    return combine_workspace_size(kCombineG1, total_shares, groups);
+}
+
+size_t hbrbc_g2_combine_workspace_size(size_t total_shares, size_t groups) {
+    return combine_workspace_size(kCombineG2, total_shares, groups);
 }
 
 // The share count is the last entry of the device-side prefix sum: one
@@ -2423,26 +2460,6 @@ static int have_device() {
     return HBRBC_OK;
 }
 
-static int lincomb_run(const void *a_prepared, size_t prepared_count, const int32_t *rows,
-                       const uint8_t *scalars, const uint32_t *offsets, size_t groups,
-                       size_t total, const uint8_t *lst, uint8_t *out96, uint8_t *out48,
-                       uint8_t *status_out, const CombineWs &w, hipStream_t s) {
-    const uint32_t *tab = static_cast<const uint32_t *>(a_prepared);
-    // the table's status bytes sit behind the coordinates of the count it was
-    // prepared with
-    const uint8_t *tst =
-        static_cast<const uint8_t *>(a_prepared) + round_up(g1_key_words(prepared_count) * 4, 256);
-    HB_HIP(launch_g1_scalar_mul(tab, tst, prepared_count, rows, scalars, total, w.pts, w.pst, s));
-    HB_HIP(launch_g1_reduce_encode(w.pts, w.pst, offsets, groups, total, lst, out96, out48,
-                                   status_out, s));
-    return HBRBC_OK;
-}
-
-size_t hbrbc_g1_combine_workspace_size(size_t total_shares, size_t groups) {
-    return round_up(g1_point_words(total_shares) * 4, 256) + round_up(total_shares, 256) +
-           round_up(total_shares * 32, 256) + round_up(groups, 256);
-}
-
 int hbrbc_lagrange_coeffs(const uint32_t *idx, const uint32_t *offsets, size_t groups,
                           uint8_t *coeffs_out, uint8_t *status_out, void *stream) {
     if (groups == 0) return HBRBC_OK;
@@ -2457,20 +2474,45 @@ int hbrbc_lagrange_coeffs(const uint32_t *idx, const uint32_t *offsets, size_t g
     return HBRBC_OK;
 }
 
-int hbrbc_g1_lincomb_prepared(const void *a_prepared, size_t prepared_count, const int32_t *rows,
-                              const uint8_t *scalars, const uint32_t *offsets, size_t groups,
-                              uint8_t *out96, uint8_t *out48, uint8_t *status_out,
-                              void *workspace, void *stream) {
+// sum_j [k_j] T[rows[j]] per group, encoded.  The scalars are the caller's
+// (`scalars`), or with `idx` the Lagrange coefficients at 0 of the node
+// indices, computed into the workspace first.  `parity` is G2's alone.
+static int lincomb_run(const CombineGroup &G, const void *table, size_t table_count,
+                       const int32_t *rows, const uint8_t *scalars, const uint32_t *idx,
+                       const uint32_t *offsets, size_t groups, uint8_t *out_u, uint8_t *out_c,
+                       uint8_t *parity, uint8_t *status_out, void *workspace, void *stream) {
     if (groups == 0) return HBRBC_OK;
-    if (!a_prepared || !offsets || !out96 || !out48 || !status_out || !workspace)
+    if (!table || !offsets || !out_u || !out_c || !status_out || !workspace)
         return fail(HBRBC_E_INVALID_ARG, "null argument");
     if (int rc = have_device()) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     size_t total = 0;
     if (int rc = combine_total(offsets, groups, s, &total)) return rc;
-    if (total && (!rows || !scalars)) return fail(HBRBC_E_INVALID_ARG, "null argument");
-    return lincomb_run(a_prepared, prepared_count, rows, scalars, offsets, groups, total, nullptr,
-                       out96, out48, status_out, combine_ws(workspace, total, groups), s);
+    if (total && (!rows || (!idx && !scalars)))
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    const CombineWs w = combine_ws(G, workspace, total);
+    if (idx) {
+        HB_HIP(hipMemsetAsync(w.lst, 0, groups, s));
+        HB_HIP(launch_lagrange(idx, offsets, groups, total, w.coeffs, w.lst, s));
+        scalars = w.coeffs;
+    }
+    // the table's status bytes sit behind the coordinates of the count it was
+    // prepared with
+    const uint8_t *tst =
+        static_cast<const uint8_t *>(table) + round_up(G.table_words(table_count) * 4, 256);
+    HB_HIP(G.scalar_mul(static_cast<const uint32_t *>(table), tst, table_count, rows, scalars,
+                        total, w.pts, w.pst, s));
+    HB_HIP(G.reduce_encode(w.pts, w.pst, offsets, groups, total, idx ? w.lst : nullptr, out_u,
+                           out_c, parity, status_out, s));
+    return HBRBC_OK;
+}
+
+int hbrbc_g1_lincomb_prepared(const void *a_prepared, size_t prepared_count, const int32_t *rows,
+                              const uint8_t *scalars, const uint32_t *offsets, size_t groups,
+                              uint8_t *out96, uint8_t *out48, uint8_t *status_out,
+                              void *workspace, void *stream) {
+    return lincomb_run(kCombineG1, a_prepared, prepared_count, rows, scalars, nullptr, offsets,
+                       groups, out96, out48, nullptr, status_out, workspace, stream);
 }
 
 int hbrbc_decrypt_combine_prepared(const void *a_prepared, size_t prepared_count,
@@ -2478,37 +2520,29 @@ int hbrbc_decrypt_combine_prepared(const void *a_prepared, size_t prepared_count
                                    const uint32_t *offsets, size_t groups, uint8_t *out96,
                                    uint8_t *out48, uint8_t *status_out, void *workspace,
                                    void *stream) {
-    if (groups == 0) return HBRBC_OK;
-    if (!a_prepared || !offsets || !out96 || !out48 || !status_out || !workspace)
-        return fail(HBRBC_E_INVALID_ARG, "null argument");
-    if (int rc = have_device()) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    size_t total = 0;
-    if (int rc = combine_total(offsets, groups, s, &total)) return rc;
-    if (total && (!rows || !idx)) return fail(HBRBC_E_INVALID_ARG, "null argument");
-    const CombineWs w = combine_ws(workspace, total, groups);
-    HB_HIP(hipMemsetAsync(w.lst, 0, groups, s));
-    HB_HIP(launch_lagrange(idx, offsets, groups, total, w.coeffs, w.lst, s));
-    return lincomb_run(a_prepared, prepared_count, rows, w.coeffs, offsets, groups, total, w.lst,
-                       out96, out48, status_out, w, s);
+    return lincomb_run(kCombineG1, a_prepared, prepared_count, rows, nullptr, idx, offsets,
+                       groups, out96, out48, nullptr, status_out, workspace, stream);
 }
 
-int hbrbc_decrypt_combine(const uint8_t *shares, const uint32_t *idx, size_t n, uint8_t out96[96],
-                          uint8_t out48[48]) {
-    if (!out96 || !out48 || (n && (!shares || !idx)))
-        return fail(HBRBC_E_INVALID_ARG, "null argument");
+// The per-call forms: one group of n shares with rows 0 .. n-1, prepared and
+// combined in one device block; out gets the uncompressed encoding, the
+// compressed one and the parity byte (3 G.enc / 2 + 1 bytes).
+static int combine_once(const CombineGroup &G, const uint8_t *shares, const uint32_t *idx,
+                        size_t n, uint8_t *out) {
     if (int rc = have_device()) return rc;
-    // device block: shares | idx | rows | offsets | out96, out48, status |
+    // device block: shares | idx | rows | offsets | encodings, parity, status |
     // prepared table | workspace
-    const size_t o_idx = round_up(n * 96, 256), o_rows = o_idx + round_up(n * 4, 256);
+    const size_t o_idx = round_up(n * G.enc, 256), o_rows = o_idx + round_up(n * 4, 256);
     const size_t o_off = o_rows + round_up(n * 4, 256), o_out = o_off + 256;
-    const size_t o_tab = o_out + 256, o_ws = o_tab + hbrbc_g1_prepared_size(n);
-    const size_t bytes = o_ws + hbrbc_g1_combine_workspace_size(n, 1);
+    const size_t o_tab = o_out + 512;
+    const size_t o_ws = o_tab + round_up(G.table_words(n) * 4, 256) + round_up(n, 256);
+    const size_t bytes = o_ws + combine_workspace_size(G, n, 1);
+    const size_t o_par = G.enc * 3 / 2, o_st = o_par + 1;
     uint8_t *dev = nullptr;
     HB_HIP(hipMalloc(&dev, bytes));
-    std::vector<uint8_t> host(o_out, 0);
+    std::vector<uint8_t> host(o_tab, 0);   // the output block too: G1 writes no parity byte
     if (n) {
-        memcpy(host.data(), shares, n * 96);
+        memcpy(host.data(), shares, n * G.enc);
         memcpy(host.data() + o_idx, idx, n * 4);
     }
     for (size_t i = 0; i < n; ++i) {
@@ -2517,24 +2551,34 @@ int hbrbc_decrypt_combine(const uint8_t *shares, const uint32_t *idx, size_t n, 
     }
     const uint32_t offs[2] = {0, (uint32_t)n};
     memcpy(host.data() + o_off, offs, sizeof offs);
-    uint8_t out[256] = {0};
+    uint8_t res[512] = {0};
     int rc = HBRBC_OK;
     hipError_t e = hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        rc = hbrbc_g1_prepare(dev, n, dev + o_tab, nullptr);
+        rc = G.prepare(dev, n, dev + o_tab, nullptr);
         if (rc == HBRBC_OK)
-            rc = hbrbc_decrypt_combine_prepared(
-                dev + o_tab, n, reinterpret_cast<const int32_t *>(dev + o_rows),
-                reinterpret_cast<const uint32_t *>(dev + o_idx),
-                reinterpret_cast<const uint32_t *>(dev + o_off), 1, dev + o_out, dev + o_out + 96,
-                dev + o_out + 144, dev + o_ws, nullptr);
-        if (rc == HBRBC_OK) e = hipMemcpy(out, dev + o_out, 145, hipMemcpyDeviceToHost);
+            rc = lincomb_run(G, dev + o_tab, n, reinterpret_cast<const int32_t *>(dev + o_rows),
+                             nullptr, reinterpret_cast<const uint32_t *>(dev + o_idx),
+                             reinterpret_cast<const uint32_t *>(dev + o_off), 1, dev + o_out,
+                             dev + o_out + G.enc, dev + o_out + o_par, dev + o_out + o_st,
+                             dev + o_ws, nullptr);
+        if (rc == HBRBC_OK) e = hipMemcpy(res, dev + o_out, o_st + 1, hipMemcpyDeviceToHost);
     }
     (void)hipFree(dev);
-    if (e != hipSuccess) return fail(HBRBC_E_DEVICE, "decrypt combine: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(HBRBC_E_DEVICE, "%s: %s", G.what, hipGetErrorString(e));
     if (rc != HBRBC_OK) return rc;
-    if (out[144] == 3) return fail(HBRBC_E_INVALID_ARG, "duplicate share index");
-    if (out[144] == 2) return fail(HBRBC_E_INVALID_ARG, "invalid curve point");
+    if (res[o_st] == 3) return fail(HBRBC_E_INVALID_ARG, "duplicate share index");
+    if (res[o_st] == 2) return fail(HBRBC_E_INVALID_ARG, "invalid curve point");
+    memcpy(out, res, o_st);
+    return HBRBC_OK;
+}
+
+int hbrbc_decrypt_combine(const uint8_t *shares, const uint32_t *idx, size_t n, uint8_t out96[96],
+                          uint8_t out48[48]) {
+    if (!out96 || !out48 || (n && (!shares || !idx)))
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    uint8_t out[145];
+    if (int rc = combine_once(kCombineG1, shares, idx, n, out)) return rc;
     memcpy(out96, out, 96);
     memcpy(out48, out + 96, 48);
     return HBRBC_OK;
@@ -2662,116 +2706,30 @@ int hbrbc_sig_check_prepared(const void *sig_table, size_t sig_count, const void
     return HBRBC_OK;
 }
 
-// workspace of the G2 combine: as CombineWs, the points over Fp2
-static CombineWs g2_combine_ws(void *workspace, size_t total) {
-    uint8_t *p = static_cast<uint8_t *>(workspace);
-    CombineWs w;
-    w.pts = reinterpret_cast<uint32_t *>(p);
-    p += round_up(g2_point_words(total) * 4, 256);
-    w.pst = p;
-    p += round_up(total, 256);
-    w.coeffs = p;
-    p += round_up(total * 32, 256);
-    w.lst = p;
-    return w;
-}
-
-size_t hbrbc_g2_combine_workspace_size(size_t total_shares, size_t groups) {
-    return round_up(g2_point_words(total_shares) * 4, 256) + round_up(total_shares, 256) +
-           round_up(total_shares * 32, 256) + round_up(groups, 256);
-}
-
-static int g2_lincomb_run(const void *table, size_t table_count, const int32_t *rows,
-                          const uint8_t *scalars, const uint32_t *offsets, size_t groups,
-                          size_t total, const uint8_t *lst, uint8_t *out192, uint8_t *out96,
-                          uint8_t *parity_out, uint8_t *status_out, const CombineWs &w,
-                          hipStream_t s) {
-    HB_HIP(launch_g2_scalar_mul(static_cast<const uint32_t *>(table),
-                                g2_points_status(table, table_count), table_count, rows, scalars,
-                                total, w.pts, w.pst, s));
-    HB_HIP(launch_g2_reduce_encode(w.pts, w.pst, offsets, groups, total, lst, out192, out96,
-                                   parity_out, status_out, s));
-    return HBRBC_OK;
-}
-
 int hbrbc_g2_lincomb_prepared(const void *sig_table, size_t sig_count, const int32_t *rows,
                               const uint8_t *scalars, const uint32_t *offsets, size_t groups,
                               uint8_t *out192, uint8_t *out96, uint8_t *parity_out,
                               uint8_t *status_out, void *workspace, void *stream) {
-    if (groups == 0) return HBRBC_OK;
-    if (!sig_table || !offsets || !out192 || !out96 || !parity_out || !status_out || !workspace)
-        return fail(HBRBC_E_INVALID_ARG, "null argument");
-    if (int rc = have_device()) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    size_t total = 0;
-    if (int rc = combine_total(offsets, groups, s, &total)) return rc;
-    if (total && (!rows || !scalars)) return fail(HBRBC_E_INVALID_ARG, "null argument");
-    return g2_lincomb_run(sig_table, sig_count, rows, scalars, offsets, groups, total, nullptr,
-                          out192, out96, parity_out, status_out, g2_combine_ws(workspace, total),
-                          s);
+    if (groups && !parity_out) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    return lincomb_run(kCombineG2, sig_table, sig_count, rows, scalars, nullptr, offsets, groups,
+                       out192, out96, parity_out, status_out, workspace, stream);
 }
 
 int hbrbc_sig_combine_prepared(const void *sig_table, size_t sig_count, const int32_t *rows,
                                const uint32_t *idx, const uint32_t *offsets, size_t groups,
                                uint8_t *out192, uint8_t *out96, uint8_t *parity_out,
                                uint8_t *status_out, void *workspace, void *stream) {
-    if (groups == 0) return HBRBC_OK;
-    if (!sig_table || !offsets || !out192 || !out96 || !parity_out || !status_out || !workspace)
-        return fail(HBRBC_E_INVALID_ARG, "null argument");
-    if (int rc = have_device()) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    size_t total = 0;
-    if (int rc = combine_total(offsets, groups, s, &total)) return rc;
-    if (total && (!rows || !idx)) return fail(HBRBC_E_INVALID_ARG, "null argument");
-    const CombineWs w = g2_combine_ws(workspace, total);
-    HB_HIP(hipMemsetAsync(w.lst, 0, groups, s));
-    HB_HIP(launch_lagrange(idx, offsets, groups, total, w.coeffs, w.lst, s));
-    return g2_lincomb_run(sig_table, sig_count, rows, w.coeffs, offsets, groups, total, w.lst,
-                          out192, out96, parity_out, status_out, w, s);
+    if (groups && !parity_out) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    return lincomb_run(kCombineG2, sig_table, sig_count, rows, nullptr, idx, offsets, groups,
+                       out192, out96, parity_out, status_out, workspace, stream);
 }
 
 int hbrbc_sig_combine(const uint8_t *shares, const uint32_t *idx, size_t n, uint8_t out192[192],
                       uint8_t out96[96], uint8_t *parity) {
     if (!out192 || !out96 || !parity || (n && (!shares || !idx)))
         return fail(HBRBC_E_INVALID_ARG, "null argument");
-    if (int rc = have_device()) return rc;
-    // device block: shares | idx | rows | offsets | out192, out96, parity,
-    // status | point table | workspace
-    const size_t o_idx = round_up(n * 192, 256), o_rows = o_idx + round_up(n * 4, 256);
-    const size_t o_off = o_rows + round_up(n * 4, 256), o_out = o_off + 256;
-    const size_t o_tab = o_out + 512, o_ws = o_tab + hbrbc_g2_points_size(n);
-    const size_t bytes = o_ws + hbrbc_g2_combine_workspace_size(n, 1);
-    uint8_t *dev = nullptr;
-    HB_HIP(hipMalloc(&dev, bytes));
-    std::vector<uint8_t> host(o_out, 0);
-    if (n) {
-        memcpy(host.data(), shares, n * 192);
-        memcpy(host.data() + o_idx, idx, n * 4);
-    }
-    for (size_t i = 0; i < n; ++i) {
-        const int32_t r = (int32_t)i;
-        memcpy(host.data() + o_rows + 4 * i, &r, 4);
-    }
-    const uint32_t offs[2] = {0, (uint32_t)n};
-    memcpy(host.data() + o_off, offs, sizeof offs);
-    uint8_t out[512] = {0};
-    int rc = HBRBC_OK;
-    hipError_t e = hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = hbrbc_g2_points_prepare(dev, n, dev + o_tab, nullptr);
-        if (rc == HBRBC_OK)
-            rc = hbrbc_sig_combine_prepared(
-                dev + o_tab, n, reinterpret_cast<const int32_t *>(dev + o_rows),
-                reinterpret_cast<const uint32_t *>(dev + o_idx),
-                reinterpret_cast<const uint32_t *>(dev + o_off), 1, dev + o_out, dev + o_out + 192,
-                dev + o_out + 288, dev + o_out + 289, dev + o_ws, nullptr);
-        if (rc == HBRBC_OK) e = hipMemcpy(out, dev + o_out, 290, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(dev);
-    if (e != hipSuccess) return fail(HBRBC_E_DEVICE, "signature combine: %s", hipGetErrorString(e));
-    if (rc != HBRBC_OK) return rc;
-    if (out[289] == 3) return fail(HBRBC_E_INVALID_ARG, "duplicate share index");
-    if (out[289] == 2) return fail(HBRBC_E_INVALID_ARG, "invalid curve point");
+    uint8_t out[289];
+    if (int rc = combine_once(kCombineG2, shares, idx, n, out)) return rc;
     memcpy(out192, out, 192);
     memcpy(out96, out + 192, 96);
     *parity = out[288];

@@ -165,14 +165,11 @@ DEV void fp_from29(Fp &r, const uint32_t (&o)[14], bool neg) {
     fp_reduce_once(r, t);
 }
 
-// HB_FP_CHAINS: independent 64-bit accumulators per column (the products of a
-// column are split round-robin over them; each v_mad_u64_u32 depends on the
-// previous one of its chain).  A/B: 2 (round 3) or 4.
-#ifndef HB_FP_CHAINS
-#define HB_FP_CHAINS 2
-#endif
+// NC independent 64-bit accumulators per column (the products of a column are
+// split round-robin over them; each v_mad_u64_u32 depends on the previous one
+// of its chain).  2 (round 3) won the A/B against 4.
 DEV void fp_mul(Fp &r, const Fp &a, const Fp &b) {
-    constexpr int NC = HB_FP_CHAINS;
+    constexpr int NC = 2;
     uint32_t x[14], y[14], m[14], o[14];
     fp_to29(x, a.l);
     fp_to29(y, b.l);
@@ -280,66 +277,25 @@ DEV void fp2_redc(Fp2 &r, Cols cols) {
     fp_from29(r.c1, o1, false);
 }
 
-// HB_LAZY_MUL / HB_LAZY_SQR: the lazily reduced Fp2 product / square (1)
-// or three / two Fp products (0) (A/B)
-#ifndef HB_LAZY_MUL
-#define HB_LAZY_MUL 0
-#endif
-#ifndef HB_LAZY_SQR
-#define HB_LAZY_SQR 1
-#endif
-#if HB_LAZY_MUL
+// The square is the lazily reduced form; the product is three Fp products
+// (the lazy product lost its A/B), with a scheduling barrier
+// between them so the scheduler cannot interleave them (fewer live digits,
+// less ILP; round 6: Miller 71.1 -> 66.8, final exp 68.8 -> 66.8 ms, r6u).
 DEV void fp2_mul_in(Fp2 &r, const Fp2 &a, const Fp2 &b) {
-    uint32_t x0[14], x1[14], y0[14], y1[14], s[14], t[14];
-    fp_to29(x0, a.c0.l);
-    fp_to29(x1, a.c1.l);
-    fp_to29(y0, b.c0.l);
-    fp_to29(y1, b.c1.l);
-#pragma unroll
-    for (int i = 0; i < 14; ++i) {
-        s[i] = x0[i] + x1[i];   // < 2^30: products < 2^60, 14 per column
-        t[i] = y0[i] + y1[i];
-    }
-    fp2_redc(r, [&](int k, uint64_t &e0, uint64_t &e1) {
-        const int lo = k > 13 ? k - 13 : 0, hi = k < 13 ? k : 13;
-        uint64_t p0 = 0, p1 = 0, p2 = 0;
-#pragma unroll
-        for (int i = lo; i <= hi; ++i) {
-            p0 += (uint64_t)x0[i] * y0[k - i];
-            p1 += (uint64_t)x1[i] * y1[k - i];
-            p2 += (uint64_t)s[i] * t[k - i];
-        }
-        e0 += p0 - p1;        // a0 b0 - a1 b1
-        e1 += p2 - p0 - p1;   // a0 b1 + a1 b0 (Karatsuba)
-    });
-}
-
-#else
-// HB_FP2_SERIAL (A/B): a scheduling barrier between the three Fp products, so
-// the scheduler cannot interleave them (fewer live digits, less ILP)
-#ifndef HB_FP2_SERIAL
-#define HB_FP2_SERIAL 1   // round 6: Miller 71.1 -> 66.8, final exp 68.8 -> 66.8 ms (r6u)
-#endif
-template <bool SER>
-DEV void fp2_mul_t(Fp2 &r, const Fp2 &a, const Fp2 &b) {
     Fp t0, t1, s0, s1;
     fp_mul(t0, a.c0, b.c0);
-    if (SER) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
     fp_mul(t1, a.c1, b.c1);
-    if (SER) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
     fp_add(s0, a.c0, a.c1);
     fp_add(s1, b.c0, b.c1);
     fp_mul(s0, s0, s1);
-    if (SER) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
     fp_sub(r.c0, t0, t1);
     fp_sub(s0, s0, t0);
     fp_sub(r.c1, s0, t1);
 }
-DEV void fp2_mul_in(Fp2 &r, const Fp2 &a, const Fp2 &b) { fp2_mul_t<HB_FP2_SERIAL != 0>(r, a, b); }
 
-#endif
-
-#if HB_LAZY_SQR
 DEV void fp2_sqr_in(Fp2 &r, const Fp2 &a) {
     uint32_t x0[14], x1[14], s[14], t2[14];
     int32_t d[14];
@@ -364,18 +320,6 @@ DEV void fp2_sqr_in(Fp2 &r, const Fp2 &a) {
         e1 += q1;
     });
 }
-
-#else
-DEV void fp2_sqr_in(Fp2 &r, const Fp2 &a) {
-    Fp s, d, m;
-    fp_add(s, a.c0, a.c1);
-    fp_sub(d, a.c0, a.c1);
-    fp_mul(m, a.c0, a.c1);
-    fp_mul(r.c0, s, d);
-    fp_dbl(r.c1, m);
-}
-
-#endif
 
 // Out-of-line forms for cold code (inversions, Frobenius, input checks); the
 // hot units (Fp6 products, the sparse line product, the cyclotomic square, the
@@ -549,10 +493,8 @@ DEV bool fp12_is_one(const Fp12 &a) {
 
 DEV void fp12_conj(Fp12 &r, const Fp12 &a) { r.c0 = a.c0; fp6_neg(r.c1, a.c1); }
 
-// HB_FE_INL: the Fp6 products of the full Fp12 product inlined into it (A/B)
-#ifndef HB_FE_INL
-#define HB_FE_INL 0
-#endif
+// INL: the Fp6 products inlined into the product (fp12_exp_by_x); the
+// out-of-line fp12_mul keeps them as calls (the inlined form lost its A/B)
 template <bool INL>
 DEV void fp12_mul_t(Fp12 &r, const Fp12 &a, const Fp12 &b) {
     Fp6 aa, bb, s, t;
@@ -566,7 +508,7 @@ DEV void fp12_mul_t(Fp12 &r, const Fp12 &a, const Fp12 &b) {
     fp6_mul_v(bb, bb);
     fp6_add(r.c0, aa, bb);
 }
-NOINL void fp12_mul(Fp12 &r, const Fp12 &a, const Fp12 &b) { fp12_mul_t<HB_FE_INL != 0>(r, a, b); }
+NOINL void fp12_mul(Fp12 &r, const Fp12 &a, const Fp12 &b) { fp12_mul_t<false>(r, a, b); }
 
 // INL: the Fp6 products inlined (no call boundary inside the unit, so no
 // stack traffic for their operands; tools/fp_microbench.hip: the same 26.8 k
@@ -628,17 +570,10 @@ NOINL void fp12_frob(Fp12 &r, const Fp12 &a, int k) {
 }
 
 // (a + b s)^2 in Fp4 = Fp2[s]/(s^2 - xi): (a^2 + xi b^2, 2ab)
-// HB_CYC_SERIAL (A/B): scheduling barriers between the Fp2 squarings of the
-// cyclotomic square (fewer live digits, less ILP)
-#ifndef HB_CYC_SERIAL
-#define HB_CYC_SERIAL 0
-#endif
 DEV void fp4_sqr(Fp2 &c0, Fp2 &c1, const Fp2 &a, const Fp2 &b) {
     Fp2 t0, t1, t2;
     fp2_sqr_in(t0, a);
-    if (HB_CYC_SERIAL) __builtin_amdgcn_sched_barrier(0);
     fp2_sqr_in(t1, b);
-    if (HB_CYC_SERIAL) __builtin_amdgcn_sched_barrier(0);
     fp2_mul_xi(t2, t1);
     fp2_add(c0, t2, t0);
     fp2_add(t2, a, b);
@@ -649,19 +584,11 @@ DEV void fp4_sqr(Fp2 &c0, Fp2 &c1, const Fp2 &a, const Fp2 &b) {
 
 // Granger-Scott squaring, valid on the cyclotomic subgroup (every value of
 // the hard part): 9 Fp2 squarings instead of the 2 Fp6 products of fp12_sqr.
-// HB_INL_CYC: inlined into fp12_exp_by_x's loop, so the running value stays
-// in registers instead of passing through the stack 62 times per call (round
-// 5, default: 262144 grouped checks 159.1 -> 157.3 ms; with 1 wave/SIMD as
-// well 168.1, profiles/r5n_f4_cyclo_inline_ab.txt)
-#ifndef HB_INL_CYC
-#define HB_INL_CYC 1
-#endif
-#if HB_INL_CYC
-DEV
-#else
-NOINL
-#endif
-void fp12_cyclo_sqr(Fp12 &f) {
+// Inlined into fp12_exp_by_x's loop, so the running value stays in registers
+// instead of passing through the stack 62 times per call (round 5: 262144
+// grouped checks 159.1 -> 157.3 ms; with 1 wave/SIMD as well 168.1,
+// profiles/r5n_f4_cyclo_inline_ab.txt)
+DEV void fp12_cyclo_sqr(Fp12 &f) {
     Fp2 z0 = f.c0.c0, z4 = f.c0.c1, z3 = f.c0.c2, z2 = f.c1.c0, z1 = f.c1.c1, z5 = f.c1.c2;
     Fp2 t0, t1, t2, t3;
     fp4_sqr(t0, t1, z0, z1);
@@ -692,18 +619,16 @@ void fp12_cyclo_sqr(Fp12 &f) {
 
 // f^x for the BLS parameter x < 0 (the crate's exp_by_x: pow by |x|, then
 // conjugate -- the inverse on the cyclotomic subgroup).  `shift` gives |x|>>1.
-// HB_EXPX_INL (A/B): 1 = the five products by `a` inlined too (Fp6 products
-// inlined), so the whole f^|x| is one unit with no call inside its loop
-#ifndef HB_EXPX_INL
-#define HB_EXPX_INL 1   // round 6, on the serialised Fp2 base: final exp 66.9 -> 59.1 ms (r6z)
-#endif
+// The five products by `a` are inlined too (Fp6 products inlined), so the
+// whole f^|x| is one unit with no call inside its loop (round 6, on the
+// serialised Fp2 base: final exp 66.9 -> 59.1 ms, r6z)
 NOINL void fp12_exp_by_x(Fp12 &r, const Fp12 &a, int shift) {
     const uint64_t e = kXAbs >> shift;
     Fp12 acc = a;
     for (int b = 62 - shift; b >= 0; --b) {
         fp12_cyclo_sqr(acc);
         if ((e >> b) & 1u) {
-            if (HB_EXPX_INL) fp12_mul_t<true>(acc, acc, a); else fp12_mul(acc, acc, a);
+            fp12_mul_t<true>(acc, acc, a);
         }
     }
     fp12_conj(r, acc);
@@ -715,46 +640,35 @@ struct G2Proj { Fp2 x, y, z; };
 // T <- 2T and the tangent line at T before it is evaluated at P, scaled by
 // 2YZ^2: L0 + (L1 xp) v + (L4 yp) v w with L0 = 3X^3 - 2Y^2 Z, L1 = -3X^2 Z,
 // L4 = 2 Y Z^2.
-// HB_G2_SERIAL (A/B): the serialised Fp2 product in the G2 line units too
-// (G2 preparation: one lane per point, latency-bound at 1/16 of the wave
-// slots, where the serialisation only lengthens the chain)
-#ifndef HB_G2_SERIAL
-#define HB_G2_SERIAL 1
-#endif
-DEV void fp2_mul_g2(Fp2 &r, const Fp2 &a, const Fp2 &b) {
-#if HB_LAZY_MUL
-    fp2_mul_in(r, a, b);
-#else
-    fp2_mul_t<HB_G2_SERIAL != 0>(r, a, b);
-#endif
-}
-
+// The G2 line units use the serialised Fp2 product too (G2 preparation: one
+// lane per point, latency-bound at 1/16 of the wave slots, where the
+// serialisation only lengthens the chain -- and still it won its A/B).
 NOINL void g2_dbl_line(G2Proj &T, Fp2 &l0, Fp2 &l1, Fp2 &l4) {
     Fp2 xx, w, s, ss, sss, rr, RR, B, h, t;
     fp2_sqr_in(xx, T.x);
     fp2_dbl(w, xx);
     fp2_add(w, w, xx);            // w = 3 X^2
-    fp2_mul_g2(s, T.y, T.z);
+    fp2_mul_in(s, T.y, T.z);
     fp2_dbl(s, s);                // s = 2 Y Z
     fp2_sqr_in(ss, s);
-    fp2_mul_g2(sss, s, ss);
-    fp2_mul_g2(rr, T.y, s);       // R = Y s = 2 Y^2 Z
+    fp2_mul_in(sss, s, ss);
+    fp2_mul_in(rr, T.y, s);       // R = Y s = 2 Y^2 Z
     fp2_sqr_in(RR, rr);
     fp2_add(B, T.x, rr);
     fp2_sqr_in(B, B);
     fp2_sub(B, B, xx);
     fp2_sub(B, B, RR);            // B = (X + R)^2 - X^2 - R^2
-    fp2_mul_g2(l0, T.x, w);
+    fp2_mul_in(l0, T.x, w);
     fp2_sub(l0, l0, rr);          // 3X^3 - 2Y^2 Z
-    fp2_mul_g2(l1, w, T.z);
+    fp2_mul_in(l1, w, T.z);
     fp2_neg(l1, l1);              // -3X^2 Z
-    fp2_mul_g2(l4, s, T.z);       // 2 Y Z^2
+    fp2_mul_in(l4, s, T.z);       // 2 Y Z^2
     fp2_sqr_in(h, w);
     fp2_sub(h, h, B);
     fp2_sub(h, h, B);             // h = w^2 - 2B
-    fp2_mul_g2(T.x, h, s);
+    fp2_mul_in(T.x, h, s);
     fp2_sub(t, B, h);
-    fp2_mul_g2(t, w, t);
+    fp2_mul_in(t, w, t);
     fp2_dbl(RR, RR);
     fp2_sub(T.y, t, RR);          // w (B - h) - 2 R^2
     T.z = sss;
@@ -765,30 +679,30 @@ NOINL void g2_dbl_line(G2Proj &T, Fp2 &l0, Fp2 &l1, Fp2 &l4) {
 // v = xq Z - X.
 NOINL void g2_add_line(G2Proj &T, const Fp2 &xq, const Fp2 &yq, Fp2 &l0, Fp2 &l1, Fp2 &l4) {
     Fp2 u, v, uu, vv, vvv, R, A, t;
-    fp2_mul_g2(u, yq, T.z);
+    fp2_mul_in(u, yq, T.z);
     fp2_sub(u, u, T.y);
-    fp2_mul_g2(v, xq, T.z);
+    fp2_mul_in(v, xq, T.z);
     fp2_sub(v, v, T.x);
-    fp2_mul_g2(l0, u, xq);
-    fp2_mul_g2(t, v, yq);
+    fp2_mul_in(l0, u, xq);
+    fp2_mul_in(t, v, yq);
     fp2_sub(l0, l0, t);
     fp2_neg(l1, u);
     l4 = v;
     fp2_sqr_in(uu, u);
     fp2_sqr_in(vv, v);
-    fp2_mul_g2(vvv, v, vv);
-    fp2_mul_g2(R, vv, T.x);
-    fp2_mul_g2(A, uu, T.z);
+    fp2_mul_in(vvv, v, vv);
+    fp2_mul_in(R, vv, T.x);
+    fp2_mul_in(A, uu, T.z);
     fp2_sub(A, A, vvv);
     fp2_sub(A, A, R);
     fp2_sub(A, A, R);             // A = uu Z - vvv - 2R
-    fp2_mul_g2(T.x, v, A);
+    fp2_mul_in(T.x, v, A);
     fp2_sub(t, R, A);
-    fp2_mul_g2(t, u, t);
-    fp2_mul_g2(vvv, vvv, T.y);
+    fp2_mul_in(t, u, t);
+    fp2_mul_in(vvv, vvv, T.y);
     fp2_sub(T.y, t, vvv);
-    fp2_mul_g2(T.z, T.z, vv);
-    fp2_mul_g2(T.z, T.z, v);      // Z vvv
+    fp2_mul_in(T.z, T.z, vv);
+    fp2_mul_in(T.z, T.z, v);      // Z vvv
 }
 
 // f <- f * line(P): the line evaluated at P = (xp, yp) (sparse (c0, c1, c4))
@@ -874,6 +788,8 @@ DEV void fe_add(Fp &r, const Fp &a, const Fp &b) { fp_add(r, a, b); }
 DEV void fe_add(Fp2 &r, const Fp2 &a, const Fp2 &b) { fp2_add(r, a, b); }
 DEV void fe_sub(Fp &r, const Fp &a, const Fp &b) { fp_sub(r, a, b); }
 DEV void fe_sub(Fp2 &r, const Fp2 &a, const Fp2 &b) { fp2_sub(r, a, b); }
+DEV void fe_zero(Fp &r) { fp_zero(r); }
+DEV void fe_zero(Fp2 &r) { fp2_zero(r); }
 DEV void fe_one(Fp &r) { fp_set(r, kOne); }
 DEV void fe_one(Fp2 &r) { fp_set(r.c0, kOne); fp_zero(r.c1); }
 // 3b: 12 on E, 12 (u + 1) on the twist
@@ -962,6 +878,108 @@ DEV void pt_mul_bits(PtProj<F> &acc, const F &x, const F &y, uint64_t hi, uint64
         const uint64_t w = b >= 64 ? hi : lo;
         if ((w >> (b & 63)) & 1u) pt_add_affine(acc, x, y);
     }
+}
+
+// p <- p + q, both projective (Renes-Costello-Batina algorithm 7 with a = 0
+// and 3b = 12 on E, 12 (u + 1) on the twist).  Complete on E(Fp), which has
+// odd order.  E'(Fp2) has even order, so the formulas are not complete on all
+// of it; they are on the order-r subgroup (odd order: no point of order 2, the
+// only exception), and every G2 operand is a checked G2 point or a sum of
+// such.  One template: cross-compiled, every kernel kept its VGPRs, spills,
+// scratch and instruction count against the former Fp and Fp2 overloads.
+template <class F>
+NOINL void pt_add_proj(PtProj<F> &p, const PtProj<F> &q) {
+    F t0, t1, t2, t3, t4, x3, y3, z3;
+    fe_mul(t0, p.x, q.x);
+    fe_mul(t1, p.y, q.y);
+    fe_mul(t2, p.z, q.z);
+    fe_add(t3, p.x, p.y);
+    fe_add(t4, q.x, q.y);
+    fe_mul(t3, t3, t4);
+    fe_add(t4, t0, t1);
+    fe_sub(t3, t3, t4);             // X1 Y2 + X2 Y1
+    fe_add(t4, p.y, p.z);
+    fe_add(x3, q.y, q.z);
+    fe_mul(t4, t4, x3);
+    fe_add(x3, t1, t2);
+    fe_sub(t4, t4, x3);             // Y1 Z2 + Y2 Z1
+    fe_add(x3, p.x, p.z);
+    fe_add(y3, q.x, q.z);
+    fe_mul(x3, x3, y3);
+    fe_add(y3, t0, t2);
+    fe_sub(y3, x3, y3);             // X1 Z2 + X2 Z1
+    fe_add(x3, t0, t0);
+    fe_add(t0, x3, t0);
+    fe_mul_b3(t2, t2);
+    fe_add(z3, t1, t2);
+    fe_sub(t1, t1, t2);
+    fe_mul_b3(y3, y3);
+    fe_mul(x3, t4, y3);
+    fe_mul(t2, t3, t1);
+    fe_sub(x3, t2, x3);
+    fe_mul(y3, y3, t0);
+    fe_mul(t1, t1, z3);
+    fe_add(y3, t1, y3);
+    fe_mul(t0, t0, t3);
+    fe_mul(z3, z3, t4);
+    fe_add(p.z, z3, t0);
+    p.x = x3;
+    p.y = y3;
+}
+
+template <class F>
+DEV void pt_identity(PtProj<F> &p) {
+    fe_zero(p.x);
+    fe_one(p.y);
+    fe_zero(p.z);
+}
+
+// Projective points between the kernels: limb-major like store_f12, word w of
+// share j at ws[w * n + j] (X, Y, Z: 36 words over Fp, 72 over Fp2).
+template <class F>
+DEV void store_pt(uint32_t *ws, size_t n, size_t j, const PtProj<F> &p) {
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(&p);
+#pragma unroll 4
+    for (int w = 0; w < (int)(sizeof(PtProj<F>) / 4); ++w) ws[(size_t)w * n + j] = src[w];
+}
+
+template <class F>
+DEV void load_pt(PtProj<F> &p, const uint32_t *ws, size_t n, size_t j) {
+    uint32_t *dst = reinterpret_cast<uint32_t *>(&p);
+#pragma unroll 4
+    for (int w = 0; w < (int)(sizeof(PtProj<F>) / 4); ++w) dst[w] = ws[(size_t)w * n + j];
+}
+
+// Affine table entries (Montgomery form): the words of x, then of y, moved as
+// uint4 -- x || y for G1 (kG1KeyWords), x.c0, x.c1, y.c0, y.c1 for G2
+// (kG2PtWords).
+constexpr int kG1KeyWords = 2 * NL;
+constexpr int kG2PtWords = 4 * NL;
+
+DEV void store_fe(uint32_t *dst, const Fp &a) {
+#pragma unroll
+    for (int w = 0; w < NL; w += 4)
+        *reinterpret_cast<uint4 *>(dst + w) = make_uint4(a.l[w], a.l[w + 1], a.l[w + 2], a.l[w + 3]);
+}
+DEV void store_fe(uint32_t *dst, const Fp2 &a) { store_fe(dst, a.c0); store_fe(dst + NL, a.c1); }
+DEV void load_fe(Fp &a, const uint32_t *src) {
+#pragma unroll
+    for (int w = 0; w < NL; w += 4) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(src + w);
+        a.l[w] = q.x; a.l[w + 1] = q.y; a.l[w + 2] = q.z; a.l[w + 3] = q.w;
+    }
+}
+DEV void load_fe(Fp2 &a, const uint32_t *src) { load_fe(a.c0, src); load_fe(a.c1, src + NL); }
+
+template <class F>
+DEV void store_affine(uint32_t *dst, const F &x, const F &y) {
+    store_fe(dst, x);
+    store_fe(dst + sizeof(F) / 4, y);
+}
+template <class F>
+DEV void load_affine(const uint32_t *src, F &x, F &y) {
+    load_fe(x, src);
+    load_fe(y, src + sizeof(F) / 4);
 }
 
 // (x, y) affine (Montgomery form), already on E: phi(P) == -[x^2] P, i.e.
@@ -1056,20 +1074,18 @@ DEV void load_f12(Fp12 &f, const uint32_t *ws, size_t n, size_t i) {
 }
 
 constexpr int kPairBlock = 64;
-// waves per SIMD of every pairing kernel (512 / HB_PAIR_WPE VGPRs per lane).
+// waves per SIMD of every pairing kernel (512 / kPairWpe VGPRs per lane).
 // The 29-bit-limb product holds x, y, m and the output digits (56 VGPRs) on
 // top of the tower operands: at 4 waves (128 VGPRs) the kernels spilled
 // (1.02 M checks/s), at 2 waves (256 VGPRs) 1.57 M, at 1 wave 1.53 M (r3,
-// tools/gpu_f4_wpe.sh; -DHB_PAIR_WPE=1|4 builds the A/B variants)
-#ifndef HB_PAIR_WPE
-#define HB_PAIR_WPE 2
-#endif
+// tools/gpu_f4_wpe.sh)
+constexpr int kPairWpe = 2;
 
 // Kernel 1: one Miller loop per lane.  Pairing i takes G1 point g1[i] and G2
 // point g2[i]; with `negate_odd`, odd pairings negate their G1 point (the
 // c of a check a,b == c,d sits at pairing 2i+1).  status[i] gets the point
 // status (max of the two); an infinity or invalid input leaves f = 1.
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void miller_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kPairWpe, kPairWpe))) void miller_kernel(
     const uint8_t *__restrict__ g1, size_t g1_stride, const uint8_t *__restrict__ g2,
     size_t g2_stride, size_t n, int pair_inputs, uint32_t *__restrict__ ws,
     uint8_t *__restrict__ status) {
@@ -1108,7 +1124,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
 // at rows 2i, 2i+1): the two Miller loops of f_a,b * f_-c,d share one
 // squaring of f per step (a multi-Miller loop; the product is what the final
 // exponentiation needs).  An infinity drops its pairing's lines (factor 1).
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void miller2_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kPairWpe, kPairWpe))) void miller2_kernel(
     const uint8_t *__restrict__ g1, const uint8_t *__restrict__ g2, size_t count,
     uint32_t *__restrict__ ws, uint8_t *__restrict__ status) {
     const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
@@ -1182,33 +1198,26 @@ DEV void load_line(const uint32_t *src, Fp2 &l0, Fp2 &l1, Fp2 &l4) {
         }
 }
 
-// HB_G2_SPLIT: the point's order-r check and its 68 lines are independent
-// chains (the lines of a point that fails the check are never read: its
-// status says invalid), so they run in two waves side by side -- block 2j
-// checks points 64j.., block 2j + 1 computes their lines (the preparation's
-// latency is the longer chain, not the sum; one ciphertext batch has only
-// 8192 points, an eighth of a wave per SIMD).  0: one lane does both.
-#ifndef HB_G2_SPLIT
-#define HB_G2_SPLIT 1
-#endif
-
-// One lane per G2 point (per role with HB_G2_SPLIT): its 68 lines, and its
-// status (0 ok, 1 infinity, 2 invalid) at pst[q].
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void g2_prepare_kernel(
+// The point's order-r check and its 68 lines are independent chains (the
+// lines of a point that fails the check are never read: its status says
+// invalid), so they run in two waves side by side -- block 2j checks points
+// 64j.., block 2j + 1 computes their lines (the preparation's latency is the
+// longer chain, not the sum; one ciphertext batch has only 8192 points, an
+// eighth of a wave per SIMD).
+//
+// One lane per G2 point and role: its 68 lines, or its status (0 ok,
+// 1 infinity, 2 invalid) at pst[q].
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kPairWpe, kPairWpe))) void g2_prepare_kernel(
     const uint8_t *__restrict__ g2, size_t count, uint32_t *__restrict__ prep,
     uint8_t *__restrict__ pst) {
-    const unsigned blk = HB_G2_SPLIT ? blockIdx.x >> 1 : blockIdx.x;
-    const size_t q = (size_t)blk * kPairBlock + threadIdx.x;
+    const size_t q = (size_t)(blockIdx.x >> 1) * kPairBlock + threadIdx.x;
     if (q >= count) return;
     Fp2 xq, yq;
-    if (HB_G2_SPLIT && !(blockIdx.x & 1)) {   // the status (wave-uniform role)
+    if (!(blockIdx.x & 1)) {   // the status (wave-uniform role)
         pst[q] = (uint8_t)decode_g2(g2 + q * 192, xq, yq);
         return;
     }
-    const int st = HB_G2_SPLIT ? decode_g2_curve(g2 + q * 192, xq, yq)
-                               : decode_g2(g2 + q * 192, xq, yq);
-    if (!HB_G2_SPLIT) pst[q] = (uint8_t)st;
-    if (st != PT_OK) return;
+    if (decode_g2_curve(g2 + q * 192, xq, yq) != PT_OK) return;
     G2Proj T;
     T.x = xq;
     T.y = yq;
@@ -1228,48 +1237,17 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
     }
 }
 
-// The prepared Miller loop's per-bit work as units of their own (A/B knob
-// HB_MILLER_INL): 0 = out-of-line squaring and line application (their
-// Fp6 operands through the stack); 1 = the squaring's Fp6 products inlined
-// into it; 2 = also the sparse product inlined into the line application.
-#ifndef HB_MILLER_INL
-#define HB_MILLER_INL 2   // round 6: Miller 85.97 -> 80.0-80.5 ms per 262,144 checks (r6e)
-#endif
-#if HB_MILLER_INL < 2
-NOINL void apply_prepared(Fp12 &f, const uint32_t *line, const Fp &xp, const Fp &yp) {
-    Fp2 l0, l1, l4;
-    load_line(line, l0, l1, l4);
-    apply_line(f, l0, l1, l4, xp, yp);
-}
-#endif
-NOINL void miller_sqr(Fp12 &f) { fp12_sqr_t<(HB_MILLER_INL >= 1)>(f, f); }
+// The prepared Miller loop's per-bit work as units of their own: the
+// squaring with its Fp6 products inlined, and the line application with the
+// sparse product inlined (their Fp6 operands do not pass through the stack;
+// round 6: Miller 85.97 -> 80.0-80.5 ms per 262,144 checks, r6e).
+NOINL void miller_sqr(Fp12 &f) { fp12_sqr_t<true>(f, f); }
 NOINL void apply_prepared_in(Fp12 &f, const uint32_t *line, const Fp &xp, const Fp &yp) {
     Fp2 l0, l1, l4, a, b;
     load_line(line, l0, l1, l4);
     fp2_mul_fp(a, l1, xp);
     fp2_mul_fp(b, l4, yp);
     fp12_mul_by_014_in(f, l0, a, b);
-}
-#if HB_MILLER_INL >= 2
-#define HB_APPLY_PREPARED apply_prepared_in
-#else
-#define HB_APPLY_PREPARED apply_prepared
-#endif
-// HB_MILLER_INL 3: the whole bit step -- the squaring and both line
-// applications -- as one unit, so f does not pass through the stack between
-// them
-DEV void apply_prepared_body(Fp12 &f, const uint32_t *line, const Fp &xp, const Fp &yp) {
-    Fp2 l0, l1, l4, a, b;
-    load_line(line, l0, l1, l4);
-    fp2_mul_fp(a, l1, xp);
-    fp2_mul_fp(b, l4, yp);
-    fp12_mul_by_014_in(f, l0, a, b);
-}
-NOINL void miller_step(Fp12 &f, const uint32_t *p1, const uint32_t *p2, const Fp &xa,
-                       const Fp &ya, const Fp &xc, const Fp &yc, bool on1, bool on2) {
-    fp12_sqr_t<true>(f, f);
-    if (on1) apply_prepared_body(f, p1, xa, ya);
-    if (on2) apply_prepared_body(f, p2, xc, yc);
 }
 
 // Prepared G1 keys: hbbft checks every decryption share against the public
@@ -1278,42 +1256,34 @@ NOINL void miller_step(Fp12 &f, const uint32_t *p1, const uint32_t *p2, const Fp
 // -- the crate holds them as curve points, so it decodes and checks them once,
 // not per share.  One lane per key: decoded and checked like any G1 input
 // (canonical coordinates, on the curve, order r), stored as Montgomery affine
-// x || y (kG1KeyWords words), status at kst[q] (0 ok, 1 infinity, 2 invalid).
-constexpr int kG1KeyWords = 2 * NL;
-
-DEV void load_g1_key(const uint32_t *src, Fp &x, Fp &y) {
-#pragma unroll
-    for (int w = 0; w < NL; w += 4) {
-        const uint4 a = *reinterpret_cast<const uint4 *>(src + w);
-        const uint4 b = *reinterpret_cast<const uint4 *>(src + NL + w);
-        x.l[w] = a.x; x.l[w + 1] = a.y; x.l[w + 2] = a.z; x.l[w + 3] = a.w;
-        y.l[w] = b.x; y.l[w + 1] = b.y; y.l[w + 2] = b.z; y.l[w + 3] = b.w;
-    }
-}
-
-// HB_G1P_WPE: waves per SIMD of the G1 preparation (affine Fp points and
-// their order-r checks need far fewer registers than the tower arithmetic)
-#ifndef HB_G1P_WPE
-#define HB_G1P_WPE HB_PAIR_WPE
-#endif
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_prepare_kernel(
-    const uint8_t *__restrict__ g1, size_t count, uint32_t *__restrict__ keys,
-    uint8_t *__restrict__ kst) {
+// x || y (store_affine), status at kst[q] (0 ok, 1 infinity, 2 invalid).
+//
+// The body of the four table kernels (G1 keys and G2 points, from either wire
+// form): one lane per point, `decode` (src + q * stride, x, y) giving the
+// Montgomery affine coordinates and the status; zeros unless valid and finite.
+template <class F, class Decode>
+DEV void prepare_table(const uint8_t *src, size_t stride, size_t count, uint32_t *tab,
+                       uint8_t *tst, Decode decode) {
     const size_t q = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
     if (q >= count) return;
-    Fp x, y;
-    const int st = decode_g1(g1 + q * 96, x, y);
+    F x, y;
+    const int st = decode(src + q * stride, x, y);
     if (st != PT_OK) {
-        fp_zero(x);
-        fp_zero(y);
+        fe_zero(x);
+        fe_zero(y);
     }
-    uint32_t *dst = keys + q * kG1KeyWords;
-#pragma unroll
-    for (int w = 0; w < NL; w += 4) {
-        *reinterpret_cast<uint4 *>(dst + w) = make_uint4(x.l[w], x.l[w + 1], x.l[w + 2], x.l[w + 3]);
-        *reinterpret_cast<uint4 *>(dst + NL + w) = make_uint4(y.l[w], y.l[w + 1], y.l[w + 2], y.l[w + 3]);
-    }
-    kst[q] = (uint8_t)st;
+    store_affine(tab + q * (2 * sizeof(F) / 4), x, y);
+    tst[q] = (uint8_t)st;
+}
+
+// kG1PrepWpe: waves per SIMD of the G1 preparation (affine Fp points and
+// their order-r checks need far fewer registers than the tower arithmetic)
+constexpr int kG1PrepWpe = kPairWpe;
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kG1PrepWpe, kG1PrepWpe))) void g1_prepare_kernel(
+    const uint8_t *__restrict__ g1, size_t count, uint32_t *__restrict__ keys,
+    uint8_t *__restrict__ kst) {
+    prepare_table<Fp>(g1, 96, count, keys, kst,
+                      [](const uint8_t *p, Fp &x, Fp &y) { return decode_g1(p, x, y); });
 }
 
 // ------------------------------------------------- decryption-share combine
@@ -1514,52 +1484,13 @@ __global__ __launch_bounds__(kPairBlock) void lagrange_kernel(
     fr_store_be32(dst, lam);
 }
 
-// Projective points between the kernels: limb-major like store_f12, word w of
-// share j at ws[w * n + j] (X, Y, Z: kPtWords words).
-constexpr int kPtWords = 3 * NL;
-
-DEV void store_pt(uint32_t *ws, size_t n, size_t j, const PtProj<Fp> &p) {
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(&p);
-#pragma unroll 4
-    for (int w = 0; w < kPtWords; ++w) ws[(size_t)w * n + j] = src[w];
-}
-
-DEV void load_pt(PtProj<Fp> &p, const uint32_t *ws, size_t n, size_t j) {
-    uint32_t *dst = reinterpret_cast<uint32_t *>(&p);
-#pragma unroll 4
-    for (int w = 0; w < kPtWords; ++w) dst[w] = ws[(size_t)w * n + j];
-}
-
-DEV void pt_identity(PtProj<Fp> &p) {
-    fp_zero(p.x);
-    fp_set(p.y, kOne);
-    fp_zero(p.z);
-}
-
-// HB_G1_GLV: the scalar multiplication through the endomorphism (1) or plain
-// double-and-add over 255 bits (0) (A/B).  phi(P) = (beta x, y)
-// = -[x^2] P on G1 (g1_in_subgroup above), so with k = k1 + k2 x^2 (k1 < x^2
-// by plain long division; k2 < 2^128 because k < r = x^4 - x^2 + 1)
-//     [k] P = [k1] P + [k2] Q,   Q = [x^2] P = (beta x, -y),
-// two 128-bit halves on one doubling chain.  Per bit the lane adds P, Q or
-// P + Q, chosen by the two bits, through one call of the projective addition
-// with a selected operand: lanes with different bits do not serialise three
-// additions, and a wave pays 128 doublings and 128 additions where the plain
-// loop with per-lane scalars pays 255 and nearly 255.
-#ifndef HB_G1_GLV
-#define HB_G1_GLV 1
-#endif
-
+// k <<= 1
 DEV void fr_shl1(Fr &k) {
 #pragma unroll
     for (int i = NR - 1; i > 0; --i) k.l[i] = (k.l[i] << 1) | (k.l[i - 1] >> 31);
     k.l[0] <<= 1;
 }
 
-#ifndef HB_G2_GLV
-#define HB_G2_GLV 1   // the same split on G2 (g2_scalar_mul_kernel below)
-#endif
-#if HB_G1_GLV || HB_G2_GLV
 // k = k1 + k2 x^2, k < r: bit-serial long division by the 128-bit x^2 (a few
 // thousand integer operations against a million in the curve arithmetic)
 DEV void glv_split(Fr k, uint64_t &k1hi, uint64_t &k1lo, uint64_t &k2hi, uint64_t &k2lo) {
@@ -1585,57 +1516,84 @@ DEV void glv_split(Fr k, uint64_t &k1hi, uint64_t &k1lo, uint64_t &k2hi, uint64_
     k2hi = qhi;
     k2lo = qlo;
 }
-#endif
 
-// p <- p + q, both projective (Renes-Costello-Batina algorithm 7 with a = 0:
-// complete, E(Fp) has odd order)
-NOINL void pt_add_proj(PtProj<Fp> &p, const PtProj<Fp> &q) {
-    Fp t0, t1, t2, t3, t4, x3, y3, z3;
-    fp_mul(t0, p.x, q.x);
-    fp_mul(t1, p.y, q.y);
-    fp_mul(t2, p.z, q.z);
-    fp_add(t3, p.x, p.y);
-    fp_add(t4, q.x, q.y);
-    fp_mul(t3, t3, t4);
-    fp_add(t4, t0, t1);
-    fp_sub(t3, t3, t4);             // X1 Y2 + X2 Y1
-    fp_add(t4, p.y, p.z);
-    fp_add(x3, q.y, q.z);
-    fp_mul(t4, t4, x3);
-    fp_add(x3, t1, t2);
-    fp_sub(t4, t4, x3);             // Y1 Z2 + Y2 Z1
-    fp_add(x3, p.x, p.z);
-    fp_add(y3, q.x, q.z);
-    fp_mul(x3, x3, y3);
-    fp_add(y3, t0, t2);
-    fp_sub(y3, x3, y3);             // X1 Z2 + X2 Z1
-    fp_add(x3, t0, t0);
-    fp_add(t0, x3, t0);
-    fe_mul_b3(t2, t2);
-    fp_add(z3, t1, t2);
-    fp_sub(t1, t1, t2);
-    fe_mul_b3(y3, y3);
-    fp_mul(x3, t4, y3);
-    fp_mul(t2, t3, t1);
-    fp_sub(x3, t2, x3);
-    fp_mul(y3, y3, t0);
-    fp_mul(t1, t1, z3);
-    fp_add(y3, t1, y3);
-    fp_mul(t0, t0, t3);
-    fp_mul(z3, z3, t4);
-    fp_add(p.z, z3, t0);
-    p.x = x3;
-    p.y = y3;
+// the next digit of the joint chain, most significant first: bit 0 from k1,
+// bit 1 from k2 (0 none, 1 P, 2 Q, 3 P + Q); the halves shift left
+DEV unsigned glv_digit(uint64_t &k1hi, uint64_t &k1lo, uint64_t &k2hi, uint64_t &k2lo) {
+    const unsigned sel = (unsigned)(k1hi >> 63) | ((unsigned)(k2hi >> 63) << 1);
+    k1hi = (k1hi << 1) | (k1lo >> 63);
+    k1lo <<= 1;
+    k2hi = (k2hi << 1) | (k2lo >> 63);
+    k2lo <<= 1;
+    return sel;
 }
 
-// Kernel: one lane per share, [k_j] P_j (HB_G1_GLV above; the plain form is
-// double-and-add over the 255 bits of k).  The complete formulas take the
-// identity as a start value and any intermediate sum, so there is no
-// leading-bit search and no special case.
+// [x^2] (x, y) by the endomorphism: (beta x, -y) on G1; on G2 psi(Q) = [x] Q
+// (g2_in_subgroup above), so psi^2(Q) = (gamma x, -y) = [x^2] Q with gamma in
+// Fp (bls_consts.hpp) -- no sign flip, unlike phi on G1, and the same shape
+// of operand.
+DEV void glv_endo(Fp &qx, Fp &qy, const Fp &x, const Fp &y) {
+    fp_set(qx, kBeta);
+    fp_mul(qx, qx, x);
+    fp_neg(qy, y);
+}
+DEV void glv_endo(Fp2 &qx, Fp2 &qy, const Fp2 &x, const Fp2 &y) {
+    Fp gamma;
+    fp_set(gamma, kGammaG2);
+    fp2_mul_fp(qx, x, gamma);
+    fp2_neg(qy, y);
+}
+
+// The scalar multiplication of both groups goes through the endomorphism (it
+// won its A/Bs against plain double-and-add over 255 bits).
+// phi(P) = (beta x, y) = -[x^2] P on G1 (g1_in_subgroup above), so with
+// k = k1 + k2 x^2 (k1 < x^2 by plain long division; k2 < 2^128 because
+// k < r = x^4 - x^2 + 1)
+//     [k] P = [k1] P + [k2] Q,   Q = [x^2] P = (beta x, -y),
+// two 128-bit halves on one doubling chain.  Per bit the lane adds P, Q or
+// P + Q, chosen by the two bits, through one call of the projective addition
+// with a selected operand: lanes with different bits do not serialise three
+// additions, and a wave pays 128 doublings and 128 additions where the plain
+// loop with per-lane scalars pays 255 and nearly 255.
+//
+// acc = [k] (x, y), k < r.  The complete formulas take the identity as a start
+// value and any intermediate sum, so there is no leading-bit search and no
+// special case; k = 0 gives the identity.
+template <class F>
+DEV void pt_mul_glv(PtProj<F> &acc, const F &x, const F &y, const Fr &k) {
+    pt_identity(acc);
+    uint64_t k1hi, k1lo, k2hi, k2lo;
+    glv_split(k, k1hi, k1lo, k2hi, k2lo);
+    PtProj<F> pp, qq, tt;   // P, Q = [x^2] P, P + Q
+    pp.x = x;
+    pp.y = y;
+    fe_one(pp.z);
+    glv_endo(qq.x, qq.y, x, y);
+    qq.z = pp.z;
+    tt = pp;
+    pt_add_proj(tt, qq);
+    const uint32_t *wp = reinterpret_cast<const uint32_t *>(&pp);
+    const uint32_t *wq = reinterpret_cast<const uint32_t *>(&qq);
+    const uint32_t *wt = reinterpret_cast<const uint32_t *>(&tt);
+    for (int b = 127; b >= 0; --b) {
+        pt_dbl(acc);
+        const unsigned sel = glv_digit(k1hi, k1lo, k2hi, k2lo);
+        if (sel) {
+            PtProj<F> op;
+            uint32_t *wo = reinterpret_cast<uint32_t *>(&op);
+#pragma unroll
+            for (int w = 0; w < (int)(sizeof(PtProj<F>) / 4); ++w)
+                wo[w] = sel == 1 ? wp[w] : (sel == 2 ? wq[w] : wt[w]);
+            pt_add_proj(acc, op);
+        }
+    }
+}
+
+// Kernel: one lane per share, [k_j] P_j (pt_mul_glv).
 // P_j = row rows[j] of a g1_prepare table of `nprep` points, k_j = 32
 // big-endian bytes.  k = 0 and a table entry at infinity give the identity;
 // k >= r, an invalid table entry and a row outside the table give pst = 2.
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_scalar_mul_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kG1PrepWpe, kG1PrepWpe))) void g1_scalar_mul_kernel(
     const uint32_t *__restrict__ tab, const uint8_t *__restrict__ tst, size_t nprep,
     const int32_t *__restrict__ rows, const uint8_t *__restrict__ scalars, size_t total,
     uint32_t *__restrict__ ws, uint8_t *__restrict__ pst) {
@@ -1648,52 +1606,12 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G
     fr_load_be32(k, scalars + 32 * j);
     if (!fr_is_canonical(k)) st = PT_BAD;
     PtProj<Fp> acc;
-    pt_identity(acc);
     if (st == PT_OK) {
         Fp x, y;
-        load_g1_key(tab + (size_t)row * kG1KeyWords, x, y);
-#if HB_G1_GLV
-        uint64_t k1hi, k1lo, k2hi, k2lo;
-        glv_split(k, k1hi, k1lo, k2hi, k2lo);
-        PtProj<Fp> pp, qq, tt;   // P, Q = (beta x, -y), P + Q
-        pp.x = x;
-        pp.y = y;
-        fp_set(pp.z, kOne);
-        fp_set(qq.x, kBeta);
-        fp_mul(qq.x, qq.x, x);
-        fp_neg(qq.y, y);
-        qq.z = pp.z;
-        tt = pp;
-        pt_add_proj(tt, qq);
-        const uint32_t *wp = reinterpret_cast<const uint32_t *>(&pp);
-        const uint32_t *wq = reinterpret_cast<const uint32_t *>(&qq);
-        const uint32_t *wt = reinterpret_cast<const uint32_t *>(&tt);
-        for (int b = 127; b >= 0; --b) {
-            pt_dbl(acc);
-            const unsigned sel = (unsigned)(k1hi >> 63) | ((unsigned)(k2hi >> 63) << 1);
-            k1hi = (k1hi << 1) | (k1lo >> 63);
-            k1lo <<= 1;
-            k2hi = (k2hi << 1) | (k2lo >> 63);
-            k2lo <<= 1;
-            if (sel) {
-                PtProj<Fp> op;
-                uint32_t *wo = reinterpret_cast<uint32_t *>(&op);
-#pragma unroll
-                for (int w = 0; w < kPtWords; ++w)
-                    wo[w] = sel == 1 ? wp[w] : (sel == 2 ? wq[w] : wt[w]);
-                pt_add_proj(acc, op);
-            }
-        }
-#else
-        // k < r < 2^255: bit 254 moves to the top of the highest limb, then
-        // the scalar shifts left one bit per step (no indexed register reads)
-        fr_shl1(k);
-        for (int b = 254; b >= 0; --b) {
-            pt_dbl(acc);
-            if (k.l[NR - 1] >> 31) pt_add_affine(acc, x, y);
-            fr_shl1(k);
-        }
-#endif
+        load_affine(tab + (size_t)row * kG1KeyWords, x, y);
+        pt_mul_glv(acc, x, y, k);
+    } else {
+        pt_identity(acc);
     }
     pst[j] = (uint8_t)(st == PT_BAD ? PT_BAD : PT_OK);
     store_pt(ws, total, j, acc);
@@ -1713,6 +1631,21 @@ DEV void store_be48_raw(uint8_t *dst, const Fp &c, uint8_t flags) {
     dst[0] |= flags;
 }
 
+// sign of y - (-y) as integers for a canonical (non-Montgomery) y, -0 = 0: the
+// comparison behind the 0x20 flag of the compressed encodings
+DEV int fp_cmp_neg(const Fp &yc) {
+    Fp nc;
+    uint32_t br = 0;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) nc.l[i] = subb(kP[i], yc.l[i], br, &br);
+    if (fp_is_zero(yc)) nc = yc;
+    int cmp = 0;
+#pragma unroll
+    for (int i = NL - 1; i >= 0; --i)
+        if (cmp == 0 && yc.l[i] != nc.l[i]) cmp = yc.l[i] > nc.l[i] ? 1 : -1;
+    return cmp;
+}
+
 // A projective result to affine with one inversion: (xm, ym) Montgomery
 // (zero for infinity) and, where the pointers are non-null, the two encodings
 // described below into buffers the caller has zeroed.  Returns CB_OK or CB_INF.
@@ -1724,26 +1657,77 @@ DEV int g1_affine_encode(const PtProj<Fp> &acc, Fp &xm, Fp &ym, uint8_t *o96, ui
         if (o48) o48[0] = 0xC0;
         return CB_INF;
     }
-    Fp zi, x, y, ny;
+    Fp zi, x, y;
     fp_inv(zi, acc.z);
     fp_mul(xm, acc.x, zi);
     fp_mul(ym, acc.y, zi);
     if (!o96 && !o48) return CB_OK;
     from_mont(x, xm);
     from_mont(y, ym);
-    // p - y against y, most significant limb first
-    uint32_t br = 0;
-#pragma unroll
-    for (int i = 0; i < NL; ++i) ny.l[i] = subb(kP[i], y.l[i], br, &br);
-    int cmp = 0;   // sign of y - (p - y)
-#pragma unroll
-    for (int i = NL - 1; i >= 0; --i)
-        if (cmp == 0 && y.l[i] != ny.l[i]) cmp = y.l[i] > ny.l[i] ? 1 : -1;
     if (o96) {
         store_be48_raw(o96, x, 0);
         store_be48_raw(o96 + 48, y, 0);
     }
-    if (o48) store_be48_raw(o48, x, (uint8_t)(0x80 | (cmp > 0 ? 0x20 : 0)));
+    if (o48) store_be48_raw(o48, x, (uint8_t)(0x80 | (fp_cmp_neg(y) > 0 ? 0x20 : 0)));
+    return CB_OK;
+}
+
+// canonical affine (x, y) on the twist as x.c1 || x.c0 || y.c1 || y.c0
+DEV void g2_store_be192(uint8_t *o192, const Fp2 &x, const Fp2 &y) {
+    store_be48_raw(o192, x.c1, 0);
+    store_be48_raw(o192 + 48, x.c0, 0);
+    store_be48_raw(o192 + 96, y.c1, 0);
+    store_be48_raw(o192 + 144, y.c0, 0);
+}
+DEV void fp2_from_mont(Fp2 &r, const Fp2 &a) { from_mont(r.c0, a.c0); from_mont(r.c1, a.c1); }
+
+// The G2 flavour, always with both encodings (into zeroed buffers) and the
+// parity byte: the XOR of all bits of the uncompressed encoding.  y against
+// -y by c1 first, by c0 only when the c1 are equal.
+DEV int g2_affine_encode(const PtProj<Fp2> &acc, uint8_t *o192, uint8_t *o96, uint8_t &par) {
+    if (fp2_is_zero(acc.z)) {
+        o192[0] = 0x40;
+        o96[0] = 0xC0;
+        par = 1;
+        return CB_INF;
+    }
+    Fp2 zi, x, y;
+    fp2_inv(zi, acc.z);
+    fp2_mul(x, acc.x, zi);
+    fp2_mul(y, acc.y, zi);
+    fp2_from_mont(x, x);
+    fp2_from_mont(y, y);
+    int cmp = fp_cmp_neg(y.c1);
+    if (cmp == 0) cmp = fp_cmp_neg(y.c0);
+    g2_store_be192(o192, x, y);
+    store_be48_raw(o96, x.c1, (uint8_t)(0x80 | (cmp > 0 ? 0x20 : 0)));
+    store_be48_raw(o96 + 48, x.c0, 0);
+    uint32_t acc32 = 0;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) acc32 ^= x.c0.l[i] ^ x.c1.l[i] ^ y.c0.l[i] ^ y.c1.l[i];
+    par = (uint8_t)(__popc(acc32) & 1);
+    return CB_OK;
+}
+
+// The front of the two reduce kernels, one lane per group g: the status from
+// the Lagrange kernel (`lst`, may be null) and the group's shares, and for an
+// ok group the sum of its projective points in acc.
+template <class F>
+DEV int reduce_group(PtProj<F> &acc, const uint32_t *ws, const uint8_t *pst,
+                     const uint32_t *offsets, size_t g, size_t total, const uint8_t *lst) {
+    size_t b, e;
+    group_range(offsets, g, total, b, e);
+    int st = (lst && lst[g] == CB_DUP) ? CB_DUP : CB_OK;
+    if (st == CB_OK)
+        for (size_t k = b; k < e; ++k)
+            if (pst[k] == PT_BAD) st = CB_BAD;
+    if (st != CB_OK) return st;
+    PtProj<F> q;
+    pt_identity(acc);
+    for (size_t k = b; k < e; ++k) {
+        load_pt(q, ws, total, k);
+        pt_add_proj(acc, q);
+    }
     return CB_OK;
 }
 
@@ -1755,32 +1739,20 @@ DEV int g1_affine_encode(const PtProj<Fp> &acc, Fp &xm, Fp &ym, uint8_t *o96, ui
 // point at infinity, 2 an invalid share / scalar / row in the group, 3 a
 // repeated index (`lst`, from lagrange_kernel; may be null); for 2 and 3
 // both outputs are zero bytes.  An empty group is the empty sum: status 1.
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_reduce_encode_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kG1PrepWpe, kG1PrepWpe))) void g1_reduce_encode_kernel(
     const uint32_t *__restrict__ ws, const uint8_t *__restrict__ pst,
     const uint32_t *__restrict__ offsets, size_t groups, size_t total,
     const uint8_t *__restrict__ lst, uint8_t *__restrict__ out96, uint8_t *__restrict__ out48,
     uint8_t *__restrict__ status) {
     const size_t g = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
     if (g >= groups) return;
-    size_t b, e;
-    group_range(offsets, g, total, b, e);
-    int st = (lst && lst[g] == CB_DUP) ? CB_DUP : CB_OK;
-    if (st == CB_OK)
-        for (size_t k = b; k < e; ++k)
-            if (pst[k] == PT_BAD) st = CB_BAD;
     uint8_t *o96 = out96 + 96 * g, *o48 = out48 + 48 * g;
     for (int i = 0; i < 96; ++i) o96[i] = 0;
     for (int i = 0; i < 48; ++i) o48[i] = 0;
-    if (st == CB_OK) {
-        PtProj<Fp> acc, q;
-        pt_identity(acc);
-        for (size_t k = b; k < e; ++k) {
-            load_pt(q, ws, total, k);
-            pt_add_proj(acc, q);
-        }
-        Fp xm, ym;
-        st = g1_affine_encode(acc, xm, ym, o96, o48);
-    }
+    PtProj<Fp> acc;
+    Fp xm, ym;
+    int st = reduce_group(acc, ws, pst, offsets, g, total, lst);
+    if (st == CB_OK) st = g1_affine_encode(acc, xm, ym, o96, o48);
     status[g] = (uint8_t)st;
 }
 
@@ -1810,7 +1782,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G
 // zero unless the status is 0; status byte 0 ok, 1 infinity, 2 invalid), so
 // it serves as the table of a second evaluation or of the check below, and,
 // where out96 / out48 are non-null, in the encodings of the combine.
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_horner_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kG1PrepWpe, kG1PrepWpe))) void g1_horner_kernel(
     const uint32_t *__restrict__ tab, const uint8_t *__restrict__ tst, size_t nprep,
     const int32_t *__restrict__ rows, const uint32_t *__restrict__ offsets, size_t polys,
     const int32_t *__restrict__ poly, const uint32_t *__restrict__ xs, size_t evals,
@@ -1843,7 +1815,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G
         const int cst = (row >= 0 && (size_t)row < nprep) ? tst[row] : PT_BAD;
         if (cst == PT_OK) {
             Fp cx, cy;
-            load_g1_key(tab + (size_t)row * kG1KeyWords, cx, cy);
+            load_affine(tab + (size_t)row * kG1KeyWords, cx, cy);
             pt_add_affine(acc, cx, cy);
         } else if (cst != PT_INF) {
             st = PT_BAD;
@@ -1861,12 +1833,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G
         fp_zero(xm);
         fp_zero(ym);
     }
-    uint32_t *dst = otab + e * kG1KeyWords;
-#pragma unroll
-    for (int w = 0; w < NL; w += 4) {
-        *reinterpret_cast<uint4 *>(dst + w) = make_uint4(xm.l[w], xm.l[w + 1], xm.l[w + 2], xm.l[w + 3]);
-        *reinterpret_cast<uint4 *>(dst + NL + w) = make_uint4(ym.l[w], ym.l[w + 1], ym.l[w + 2], ym.l[w + 3]);
-    }
+    store_affine(otab + e * kG1KeyWords, xm, ym);
     ost[e] = (uint8_t)st;
     status[e] = (uint8_t)st;
 }
@@ -1880,7 +1847,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G
 // projective against affine: X == x Z, Y == y Z, Z != 0; a table entry at
 // infinity equals a result at infinity.  ok: 1 equal, 0 not, 2 for an invalid
 // table entry, a row outside the table or s >= r.
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_base_mul_check_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kG1PrepWpe, kG1PrepWpe))) void g1_base_mul_check_kernel(
     const uint32_t *__restrict__ tab, const uint8_t *__restrict__ tst, size_t nprep,
     const int32_t *__restrict__ rows, const uint8_t *__restrict__ scalars, size_t count,
     uint8_t *__restrict__ ok) {
@@ -1901,11 +1868,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G
     pt_identity(acc);
     for (int b = 127; b >= 0; --b) {
         pt_dbl(acc);
-        const unsigned sel = (unsigned)(k1hi >> 63) | ((unsigned)(k2hi >> 63) << 1);
-        k1hi = (k1hi << 1) | (k1lo >> 63);
-        k1lo <<= 1;
-        k2hi = (k2hi << 1) | (k2lo >> 63);
-        k2lo <<= 1;
+        const unsigned sel = glv_digit(k1hi, k1lo, k2hi, k2lo);
         if (sel) {
             Fp ox, oy;
 #pragma unroll
@@ -1921,7 +1884,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G
         eq = fp_is_zero(acc.z);
     } else {
         Fp x, y, l, r;
-        load_g1_key(tab + (size_t)row * kG1KeyWords, x, y);
+        load_affine(tab + (size_t)row * kG1KeyWords, x, y);
         fp_mul(l, x, acc.z);
         fp_mul(r, y, acc.z);
         eq = !fp_is_zero(acc.z) && fp_eq(l, acc.x) && fp_eq(r, acc.y);
@@ -1940,7 +1903,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G
 // `count` shares (entry i, statuses `ast`), so the share decoding -- an
 // order-r check each -- runs as its own launch beside the G2 preparation.
 template <bool KEYS, bool PTS = false>
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void miller_prepared_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kPairWpe, kPairWpe))) void miller_prepared_kernel(
     const uint8_t *__restrict__ g1, const uint32_t *__restrict__ keys,
     const uint8_t *__restrict__ kst, const uint32_t *__restrict__ ic, size_t nkeys,
     const uint32_t *__restrict__ prep,
@@ -1955,7 +1918,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
     if constexpr (KEYS) {
         if constexpr (PTS) {
             sa = ast[i];
-            load_g1_key(atab + i * kG1KeyWords, xa, ya);   // zeros unless the point is valid
+            load_affine(atab + i * kG1KeyWords, xa, ya);   // zeros unless the point is valid
         } else {
             sa = decode_g1(g1 + i * 96, xa, ya);
         }
@@ -1963,7 +1926,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
         // an index past the key table is an invalid input, never an out-of-bounds read
         sc = qc < nkeys ? kst[qc] : PT_BAD;
         if (sc == PT_OK) {
-            load_g1_key(keys + (size_t)qc * kG1KeyWords, xc, yc);
+            load_affine(keys + (size_t)qc * kG1KeyWords, xc, yc);
         } else {
             fp_zero(xc);
             fp_zero(yc);
@@ -1987,18 +1950,14 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
         const uint32_t *p1 = prep + (size_t)qb * kLines * kLineWords;
         const uint32_t *p2 = prep + (size_t)qd * kLines * kLineWords;
         for (int b = 62; b >= 0; --b) {
-            if (HB_MILLER_INL >= 3) {
-                miller_step(f, p1, p2, xa, ya, xc, yc, on1, on2);
-            } else {
-                if (HB_MILLER_INL) miller_sqr(f); else fp12_sqr(f, f);
-                if (on1) HB_APPLY_PREPARED(f, p1, xa, ya);
-                if (on2) HB_APPLY_PREPARED(f, p2, xc, yc);
-            }
+            miller_sqr(f);
+            if (on1) apply_prepared_in(f, p1, xa, ya);
+            if (on2) apply_prepared_in(f, p2, xc, yc);
             p1 += kLineWords;
             p2 += kLineWords;
             if ((kXAbs >> b) & 1u) {
-                if (on1) HB_APPLY_PREPARED(f, p1, xa, ya);
-                if (on2) HB_APPLY_PREPARED(f, p2, xc, yc);
+                if (on1) apply_prepared_in(f, p1, xa, ya);
+                if (on2) apply_prepared_in(f, p2, xc, yc);
                 p1 += kLineWords;
                 p2 += kLineWords;
             }
@@ -2022,45 +1981,14 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
 // shares are decoded and order-checked once into a table of affine points
 // (g2_points_kernel, the G2 twin of g1_prepare_kernel), from which the check
 // walks its twist chain and the combine takes its operands.
-constexpr int kG2PtWords = 4 * NL;   // x.c0, x.c1, y.c0, y.c1 (Montgomery)
-
-DEV void load_g2_pt(const uint32_t *src, Fp2 &x, Fp2 &y) {
-    Fp *v[4] = {&x.c0, &x.c1, &y.c0, &y.c1};
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int w = 0; w < NL; w += 4) {
-            const uint4 q = *reinterpret_cast<const uint4 *>(src + e * NL + w);
-            v[e]->l[w] = q.x;
-            v[e]->l[w + 1] = q.y;
-            v[e]->l[w + 2] = q.z;
-            v[e]->l[w + 3] = q.w;
-        }
-}
-
 // One lane per G2 point: decoded and checked (canonical coordinates, on the
 // twist, order r), stored as Montgomery affine coordinates (zeros unless the
 // point is valid and finite), status at gst[q] (0 ok, 1 infinity, 2 invalid).
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void g2_points_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kPairWpe, kPairWpe))) void g2_points_kernel(
     const uint8_t *__restrict__ g2, size_t count, uint32_t *__restrict__ tab,
     uint8_t *__restrict__ gst) {
-    const size_t q = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
-    if (q >= count) return;
-    Fp2 x, y;
-    const int st = decode_g2(g2 + q * 192, x, y);
-    if (st != PT_OK) {
-        fp2_zero(x);
-        fp2_zero(y);
-    }
-    const Fp *v[4] = {&x.c0, &x.c1, &y.c0, &y.c1};
-    uint32_t *dst = tab + q * kG2PtWords;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int w = 0; w < NL; w += 4)
-            *reinterpret_cast<uint4 *>(dst + e * NL + w) =
-                make_uint4(v[e]->l[w], v[e]->l[w + 1], v[e]->l[w + 2], v[e]->l[w + 3]);
-    gst[q] = (uint8_t)st;
+    prepare_table<Fp2>(g2, 192, count, tab, gst,
+                       [](const uint8_t *p, Fp2 &x, Fp2 &y) { return decode_g2(p, x, y); });
 }
 
 // One lane per check e(K[ic[i]], P[ih[i]]) == e(G1::one(), S[i]), evaluated as
@@ -2071,7 +1999,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
 // lines at the constant -G1::one().  Both legs share one squaring of f per
 // bit.  An invalid point, an index past its table or i >= nsig gives status 2;
 // an infinity drops its leg.
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void miller_sig_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kPairWpe, kPairWpe))) void miller_sig_kernel(
     const uint32_t *__restrict__ stab, const uint8_t *__restrict__ sst, size_t nsig,
     const uint32_t *__restrict__ keys, const uint8_t *__restrict__ kst,
     const uint32_t *__restrict__ ic, size_t nkeys, const uint32_t *__restrict__ prep,
@@ -2088,7 +2016,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
     if (qh >= points) qh = 0;
     Fp xk, yk;
     if (sk == PT_OK) {
-        load_g1_key(keys + (size_t)qk * kG1KeyWords, xk, yk);
+        load_affine(keys + (size_t)qk * kG1KeyWords, xk, yk);
     } else {
         fp_zero(xk);
         fp_zero(yk);
@@ -2105,7 +2033,7 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
         Fp2 xs, ys;
         G2Proj T;
         if (on2) {
-            load_g2_pt(stab + i * kG2PtWords, xs, ys);
+            load_affine(stab + i * kG2PtWords, xs, ys);
         } else {
             fp2_zero(xs);
             fp2_zero(ys);
@@ -2116,12 +2044,12 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
         fp_zero(T.z.c1);
         const uint32_t *p1 = prep + (size_t)qh * kLines * kLineWords;
         for (int b = 62; b >= 0; --b) {
-            if (HB_MILLER_INL) miller_sqr(f); else fp12_sqr(f, f);
-            if (on1) HB_APPLY_PREPARED(f, p1, xk, yk);
+            miller_sqr(f);
+            if (on1) apply_prepared_in(f, p1, xk, yk);
             if (on2) miller_dbl(T, f, gx, gy);
             p1 += kLineWords;
             if ((kXAbs >> b) & 1u) {
-                if (on1) HB_APPLY_PREPARED(f, p1, xk, yk);
+                if (on1) apply_prepared_in(f, p1, xk, yk);
                 if (on2) miller_add(T, f, xs, ys, gx, gy);
                 p1 += kLineWords;
             }
@@ -2132,88 +2060,11 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
     store_f12(ws, count, i, f);
 }
 
-// Projective G2 points between the kernels: limb-major like store_pt
-// (X, Y, Z over Fp2: kPt2Words words).
-constexpr int kPt2Words = 6 * NL;
-
-DEV void store_pt(uint32_t *ws, size_t n, size_t j, const PtProj<Fp2> &p) {
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(&p);
-#pragma unroll 4
-    for (int w = 0; w < kPt2Words; ++w) ws[(size_t)w * n + j] = src[w];
-}
-
-DEV void load_pt(PtProj<Fp2> &p, const uint32_t *ws, size_t n, size_t j) {
-    uint32_t *dst = reinterpret_cast<uint32_t *>(&p);
-#pragma unroll 4
-    for (int w = 0; w < kPt2Words; ++w) dst[w] = ws[(size_t)w * n + j];
-}
-
-DEV void pt_identity(PtProj<Fp2> &p) {
-    fp2_zero(p.x);
-    fe_one(p.y);
-    fp2_zero(p.z);
-}
-
-// p <- p + q on the twist, both projective: pt_add_proj above over Fp2 (the
-// same algorithm 7 with a = 0 and 3b = 12 (u + 1)).  E'(Fp2) has even order,
-// so the formulas are not complete on all of it; they are on the order-r
-// subgroup (odd order: no point of order 2, the only exception), and every
-// operand here is a checked G2 point or a sum of such.  An overload, not a
-// template: the G1 kernels keep the code they were measured with.
-NOINL void pt_add_proj(PtProj<Fp2> &p, const PtProj<Fp2> &q) {
-    Fp2 t0, t1, t2, t3, t4, x3, y3, z3;
-    fe_mul(t0, p.x, q.x);
-    fe_mul(t1, p.y, q.y);
-    fe_mul(t2, p.z, q.z);
-    fe_add(t3, p.x, p.y);
-    fe_add(t4, q.x, q.y);
-    fe_mul(t3, t3, t4);
-    fe_add(t4, t0, t1);
-    fe_sub(t3, t3, t4);             // X1 Y2 + X2 Y1
-    fe_add(t4, p.y, p.z);
-    fe_add(x3, q.y, q.z);
-    fe_mul(t4, t4, x3);
-    fe_add(x3, t1, t2);
-    fe_sub(t4, t4, x3);             // Y1 Z2 + Y2 Z1
-    fe_add(x3, p.x, p.z);
-    fe_add(y3, q.x, q.z);
-    fe_mul(x3, x3, y3);
-    fe_add(y3, t0, t2);
-    fe_sub(y3, x3, y3);             // X1 Z2 + X2 Z1
-    fe_add(x3, t0, t0);
-    fe_add(t0, x3, t0);
-    fe_mul_b3(t2, t2);
-    fe_add(z3, t1, t2);
-    fe_sub(t1, t1, t2);
-    fe_mul_b3(y3, y3);
-    fe_mul(x3, t4, y3);
-    fe_mul(t2, t3, t1);
-    fe_sub(x3, t2, x3);
-    fe_mul(y3, y3, t0);
-    fe_mul(t1, t1, z3);
-    fe_add(y3, t1, y3);
-    fe_mul(t0, t0, t3);
-    fe_mul(z3, z3, t4);
-    fe_add(p.z, z3, t0);
-    p.x = x3;
-    p.y = y3;
-}
-
-// HB_G2_GLV: the G2 scalar multiplication through the endomorphism (1) or
-// plain double-and-add over 255 bits (0) (A/B).  psi(Q) = [x] Q
-// on G2 (g2_in_subgroup above), so psi^2(Q) = (gamma x, -y) = [x^2] Q with
-// gamma in Fp (bls_consts.hpp) -- no sign flip, unlike phi on G1, and the
-// same shape of operand: with k = k1 + k2 x^2 (glv_split, unchanged)
-//     [k] Q = [k1] Q + [k2] psi^2(Q),
-// two 128-bit halves on one doubling chain, one selected-operand addition per
-// bit pair as in g1_scalar_mul_kernel.  HB_G2_GLV = 1 is the default (set
-// beside HB_G1_GLV), -DHB_G2_GLV=0 builds the plain form.
-
-// Kernel: one lane per share, [k_j] Q_j.  Q_j = row rows[j] of a g2_points
+// Kernel: one lane per share, [k_j] Q_j (pt_mul_glv).  Q_j = row rows[j] of a g2_points
 // table of `nprep` points, k_j = 32 big-endian bytes.  k = 0 and a table entry
 // at infinity give the identity; k >= r, an invalid table entry and a row
 // outside the table give pst = 2.
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void g2_scalar_mul_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kPairWpe, kPairWpe))) void g2_scalar_mul_kernel(
     const uint32_t *__restrict__ tab, const uint8_t *__restrict__ tst, size_t nprep,
     const int32_t *__restrict__ rows, const uint8_t *__restrict__ scalars, size_t total,
     uint32_t *__restrict__ ws, uint8_t *__restrict__ pst) {
@@ -2226,51 +2077,12 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
     fr_load_be32(k, scalars + 32 * j);
     if (!fr_is_canonical(k)) st = PT_BAD;
     PtProj<Fp2> acc;
-    pt_identity(acc);
     if (st == PT_OK) {
         Fp2 x, y;
-        load_g2_pt(tab + (size_t)row * kG2PtWords, x, y);
-#if HB_G2_GLV
-        uint64_t k1hi, k1lo, k2hi, k2lo;
-        glv_split(k, k1hi, k1lo, k2hi, k2lo);
-        PtProj<Fp2> pp, qq, tt;   // Q, psi^2(Q) = (gamma x, -y), their sum
-        Fp gamma;
-        pp.x = x;
-        pp.y = y;
-        fe_one(pp.z);
-        fp_set(gamma, kGammaG2);
-        fp2_mul_fp(qq.x, x, gamma);
-        fp2_neg(qq.y, y);
-        qq.z = pp.z;
-        tt = pp;
-        pt_add_proj(tt, qq);
-        const uint32_t *wp = reinterpret_cast<const uint32_t *>(&pp);
-        const uint32_t *wq = reinterpret_cast<const uint32_t *>(&qq);
-        const uint32_t *wt = reinterpret_cast<const uint32_t *>(&tt);
-        for (int b = 127; b >= 0; --b) {
-            pt_dbl(acc);
-            const unsigned sel = (unsigned)(k1hi >> 63) | ((unsigned)(k2hi >> 63) << 1);
-            k1hi = (k1hi << 1) | (k1lo >> 63);
-            k1lo <<= 1;
-            k2hi = (k2hi << 1) | (k2lo >> 63);
-            k2lo <<= 1;
-            if (sel) {
-                PtProj<Fp2> op;
-                uint32_t *wo = reinterpret_cast<uint32_t *>(&op);
-#pragma unroll
-                for (int w = 0; w < kPt2Words; ++w)
-                    wo[w] = sel == 1 ? wp[w] : (sel == 2 ? wq[w] : wt[w]);
-                pt_add_proj(acc, op);
-            }
-        }
-#else
-        fr_shl1(k);   // bit 254 to the top, then one bit per step
-        for (int b = 254; b >= 0; --b) {
-            pt_dbl(acc);
-            if (k.l[NR - 1] >> 31) pt_add_affine(acc, x, y);
-            fr_shl1(k);
-        }
-#endif
+        load_affine(tab + (size_t)row * kG2PtWords, x, y);
+        pt_mul_glv(acc, x, y, k);
+    } else {
+        pt_identity(acc);
     }
     pst[j] = (uint8_t)(st == PT_BAD ? PT_BAD : PT_OK);
     store_pt(ws, total, j, acc);
@@ -2285,71 +2097,20 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_P
 // all bits of the uncompressed encoding (threshold_crypto's
 // Signature::parity(), the coin).  status as g1_reduce_encode_kernel; for 2
 // and 3 all three outputs are zero bytes.  An empty group is status 1.
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void g2_reduce_encode_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kPairWpe, kPairWpe))) void g2_reduce_encode_kernel(
     const uint32_t *__restrict__ ws, const uint8_t *__restrict__ pst,
     const uint32_t *__restrict__ offsets, size_t groups, size_t total,
     const uint8_t *__restrict__ lst, uint8_t *__restrict__ out192, uint8_t *__restrict__ out96,
     uint8_t *__restrict__ parity, uint8_t *__restrict__ status) {
     const size_t g = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
     if (g >= groups) return;
-    size_t b, e;
-    group_range(offsets, g, total, b, e);
-    int st = (lst && lst[g] == CB_DUP) ? CB_DUP : CB_OK;
-    if (st == CB_OK)
-        for (size_t k = b; k < e; ++k)
-            if (pst[k] == PT_BAD) st = CB_BAD;
     uint8_t *o192 = out192 + 192 * g, *o96 = out96 + 96 * g;
     for (int i = 0; i < 192; ++i) o192[i] = 0;
     for (int i = 0; i < 96; ++i) o96[i] = 0;
     uint8_t par = 0;
-    if (st == CB_OK) {
-        PtProj<Fp2> acc, q;
-        pt_identity(acc);
-        for (size_t k = b; k < e; ++k) {
-            load_pt(q, ws, total, k);
-            pt_add_proj(acc, q);
-        }
-        if (fp2_is_zero(acc.z)) {
-            st = CB_INF;
-            o192[0] = 0x40;
-            o96[0] = 0xC0;
-            par = 1;
-        } else {
-            Fp2 zi, x, y;
-            fp2_inv(zi, acc.z);
-            fp2_mul(x, acc.x, zi);
-            fp2_mul(y, acc.y, zi);
-            from_mont(x.c0, x.c0);
-            from_mont(x.c1, x.c1);
-            from_mont(y.c0, y.c0);
-            from_mont(y.c1, y.c1);
-            // -y = (p - c0, p - c1), a zero coefficient staying zero; y against
-            // -y by c1, most significant limb first, then by c0
-            int cmp = 0;   // sign of y - (-y)
-#pragma unroll
-            for (int c = 1; c >= 0; --c) {
-                const Fp &yc = c ? y.c1 : y.c0;
-                Fp nc;
-                uint32_t br = 0;
-#pragma unroll
-                for (int i = 0; i < NL; ++i) nc.l[i] = subb(kP[i], yc.l[i], br, &br);
-                if (fp_is_zero(yc)) nc = yc;
-#pragma unroll
-                for (int i = NL - 1; i >= 0; --i)
-                    if (cmp == 0 && yc.l[i] != nc.l[i]) cmp = yc.l[i] > nc.l[i] ? 1 : -1;
-            }
-            store_be48_raw(o192, x.c1, 0);
-            store_be48_raw(o192 + 48, x.c0, 0);
-            store_be48_raw(o192 + 96, y.c1, 0);
-            store_be48_raw(o192 + 144, y.c0, 0);
-            store_be48_raw(o96, x.c1, (uint8_t)(0x80 | (cmp > 0 ? 0x20 : 0)));
-            store_be48_raw(o96 + 48, x.c0, 0);
-            uint32_t acc32 = 0;
-#pragma unroll
-            for (int i = 0; i < NL; ++i) acc32 ^= x.c0.l[i] ^ x.c1.l[i] ^ y.c0.l[i] ^ y.c1.l[i];
-            par = (uint8_t)(__popc(acc32) & 1);
-        }
-    }
+    PtProj<Fp2> acc;
+    int st = reduce_group(acc, ws, pst, offsets, g, total, lst);
+    if (st == CB_OK) st = g2_affine_encode(acc, o192, o96, par);
     parity[g] = par;
     status[g] = (uint8_t)st;
 }
@@ -2388,21 +2149,6 @@ NOINL void fp_pow_sqrt(Fp &r, const Fp &a) {
         if (d) fp_mul(acc, acc, tab[d - 1]);
     }
     r = acc;
-}
-
-// sign of y - (-y) as integers for a canonical (non-Montgomery) y, -0 = 0:
-// the comparison of g1_reduce_encode_kernel / g2_reduce_encode_kernel
-DEV int fp_cmp_neg(const Fp &yc) {
-    Fp nc;
-    uint32_t br = 0;
-#pragma unroll
-    for (int i = 0; i < NL; ++i) nc.l[i] = subb(kP[i], yc.l[i], br, &br);
-    if (fp_is_zero(yc)) nc = yc;
-    int cmp = 0;
-#pragma unroll
-    for (int i = NL - 1; i >= 0; --i)
-        if (cmp == 0 && yc.l[i] != nc.l[i]) cmp = yc.l[i] > nc.l[i] ? 1 : -1;
-    return cmp;
 }
 
 DEV int decompress_g1(const uint8_t *src, Fp &x, Fp &y) {
@@ -2493,99 +2239,72 @@ DEV int decompress_g2(const uint8_t *src, Fp2 &x, Fp2 &y) {
 // units: pt_dbl and pt_add_affine take their operands by reference, so no
 // occupancy frees that kernel of scratch either) and the window table, which
 // is indexed by the digit and so could stay in registers only fully unrolled.
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_prepare_compressed_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kG1PrepWpe, kG1PrepWpe))) void g1_prepare_compressed_kernel(
     const uint8_t *__restrict__ g1c, size_t count, uint32_t *__restrict__ keys,
     uint8_t *__restrict__ kst) {
-    const size_t q = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
-    if (q >= count) return;
-    Fp x, y;
-    const int st = decompress_g1(g1c + q * 48, x, y);
-    if (st != PT_OK) {
-        fp_zero(x);
-        fp_zero(y);
-    }
-    uint32_t *dst = keys + q * kG1KeyWords;
-#pragma unroll
-    for (int w = 0; w < NL; w += 4) {
-        *reinterpret_cast<uint4 *>(dst + w) = make_uint4(x.l[w], x.l[w + 1], x.l[w + 2], x.l[w + 3]);
-        *reinterpret_cast<uint4 *>(dst + NL + w) = make_uint4(y.l[w], y.l[w + 1], y.l[w + 2], y.l[w + 3]);
-    }
-    kst[q] = (uint8_t)st;
+    prepare_table<Fp>(g1c, 48, count, keys, kst,
+                      [](const uint8_t *p, Fp &x, Fp &y) { return decompress_g1(p, x, y); });
 }
 
 // g2_points_kernel for compressed input (96 bytes per point): the same table.
 // Waves per SIMD: 2 like g2_points_kernel: the Fp2 chain of g2_in_subgroup
 // sets the register need, the Fp roots add none (hipcc -S: 256 VGPRs, 2
 // spilled, 1572 bytes of scratch against 4 and 1684 of g2_points_kernel).
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void g2_points_compressed_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kPairWpe, kPairWpe))) void g2_points_compressed_kernel(
     const uint8_t *__restrict__ g2c, size_t count, uint32_t *__restrict__ tab,
     uint8_t *__restrict__ gst) {
-    const size_t q = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
-    if (q >= count) return;
-    Fp2 x, y;
-    const int st = decompress_g2(g2c + q * 96, x, y);
-    if (st != PT_OK) {
-        fp2_zero(x);
-        fp2_zero(y);
-    }
-    const Fp *v[4] = {&x.c0, &x.c1, &y.c0, &y.c1};
-    uint32_t *dst = tab + q * kG2PtWords;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int w = 0; w < NL; w += 4)
-            *reinterpret_cast<uint4 *>(dst + e * NL + w) =
-                make_uint4(v[e]->l[w], v[e]->l[w + 1], v[e]->l[w + 2], v[e]->l[w + 3]);
-    gst[q] = (uint8_t)st;
+    prepare_table<Fp2>(g2c, 96, count, tab, gst,
+                       [](const uint8_t *p, Fp2 &x, Fp2 &y) { return decompress_g2(p, x, y); });
 }
 
-// Compressed to uncompressed, one lane per point: out96 + 96 q gets x || y
-// (zero bytes for an invalid point, 0x40 and zeros for infinity), status[q]
-// 0 ok, 1 infinity, 2 invalid.  For points that go on to an entry taking the
+// a Montgomery affine point as canonical big-endian x || y (G2: x.c1 || x.c0 ||
+// y.c1 || y.c0)
+DEV void store_be_affine(uint8_t *o, Fp x, Fp y) {
+    from_mont(x, x);
+    from_mont(y, y);
+    store_be48_raw(o, x, 0);
+    store_be48_raw(o + 48, y, 0);
+}
+DEV void store_be_affine(uint8_t *o, Fp2 x, Fp2 y) {
+    fp2_from_mont(x, x);
+    fp2_from_mont(y, y);
+    g2_store_be192(o, x, y);
+}
+
+// Compressed to uncompressed, one lane per point: out + 2 * stride * q gets the
+// uncompressed encoding of the `stride` bytes at src + stride * q (zero bytes
+// for an invalid point, 0x40 and zeros for infinity), status[q] 0 ok,
+// 1 infinity, 2 invalid.  For points that go on to an entry taking the
 // uncompressed form (a ciphertext's U and W).
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_G1P_WPE, HB_G1P_WPE))) void g1_decompress_kernel(
+template <class F, class Decompress>
+DEV void decompress_points(const uint8_t *src, size_t stride, size_t count, uint8_t *out,
+                           uint8_t *status, Decompress decompress) {
+    const size_t q = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (q >= count) return;
+    F x, y;
+    const int st = decompress(src + q * stride, x, y);
+    uint8_t *o = out + q * (2 * stride);
+    if (st == PT_OK) {
+        store_be_affine(o, x, y);
+    } else {
+        for (size_t i = 0; i < 2 * stride; ++i) o[i] = 0;
+        if (st == PT_INF) o[0] = 0x40;
+    }
+    status[q] = (uint8_t)st;
+}
+
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kG1PrepWpe, kG1PrepWpe))) void g1_decompress_kernel(
     const uint8_t *__restrict__ g1c, size_t count, uint8_t *__restrict__ out96,
     uint8_t *__restrict__ status) {
-    const size_t q = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
-    if (q >= count) return;
-    Fp x, y;
-    const int st = decompress_g1(g1c + q * 48, x, y);
-    uint8_t *o = out96 + q * 96;
-    if (st == PT_OK) {
-        from_mont(x, x);
-        from_mont(y, y);
-        store_be48_raw(o, x, 0);
-        store_be48_raw(o + 48, y, 0);
-    } else {
-        for (int i = 0; i < 96; ++i) o[i] = 0;
-        if (st == PT_INF) o[0] = 0x40;
-    }
-    status[q] = (uint8_t)st;
+    decompress_points<Fp>(g1c, 48, count, out96, status,
+                          [](const uint8_t *p, Fp &x, Fp &y) { return decompress_g1(p, x, y); });
 }
 
-// The same for G2: out192 + 192 q gets x.c1 || x.c0 || y.c1 || y.c0.
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_PAIR_WPE, HB_PAIR_WPE))) void g2_decompress_kernel(
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kPairWpe, kPairWpe))) void g2_decompress_kernel(
     const uint8_t *__restrict__ g2c, size_t count, uint8_t *__restrict__ out192,
     uint8_t *__restrict__ status) {
-    const size_t q = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
-    if (q >= count) return;
-    Fp2 x, y;
-    const int st = decompress_g2(g2c + q * 96, x, y);
-    uint8_t *o = out192 + q * 192;
-    if (st == PT_OK) {
-        from_mont(x.c0, x.c0);
-        from_mont(x.c1, x.c1);
-        from_mont(y.c0, y.c0);
-        from_mont(y.c1, y.c1);
-        store_be48_raw(o, x.c1, 0);
-        store_be48_raw(o + 48, x.c0, 0);
-        store_be48_raw(o + 96, y.c1, 0);
-        store_be48_raw(o + 144, y.c0, 0);
-    } else {
-        for (int i = 0; i < 192; ++i) o[i] = 0;
-        if (st == PT_INF) o[0] = 0x40;
-    }
-    status[q] = (uint8_t)st;
+    decompress_points<Fp2>(g2c, 96, count, out192, status,
+                           [](const uint8_t *p, Fp2 &x, Fp2 &y) { return decompress_g2(p, x, y); });
 }
 
 // The crate's final exponentiation (Bls12::final_exponentiation): easy part
@@ -2637,10 +2356,8 @@ DEV void store_be48(uint8_t *dst, const Fp &a) {
 // (1: a pairing, 2: a check) are multiplied first.  gt_out (if set) gets the
 // 576-byte GT value; ok_out (if set) gets 1 if the value is 1 (the check
 // holds), 0 if not, 2 if an input point was invalid.
-#ifndef HB_FE_WPE
-#define HB_FE_WPE HB_PAIR_WPE   // A/B: the final exponentiation's own occupancy
-#endif
-__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(HB_FE_WPE, HB_FE_WPE))) void final_exp_kernel(
+constexpr int kFinalExpWpe = kPairWpe;   // the final exponentiation's own occupancy
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kFinalExpWpe, kFinalExpWpe))) void final_exp_kernel(
     const uint32_t *__restrict__ ws, size_t n_miller, size_t n_out, int per_out,
     const uint8_t *__restrict__ status, uint8_t *__restrict__ gt_out,
     uint8_t *__restrict__ ok_out) {
@@ -2698,7 +2415,7 @@ size_t pairing_prepared_words(size_t points) { return points * (size_t)kLines * 
 hipError_t launch_g2_prepare(const uint8_t *g2, size_t count, uint32_t *prep, uint8_t *pst,
                              hipStream_t s) {
     if (count == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock) * (HB_G2_SPLIT ? 2 : 1);
+    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock) * 2;
     hipLaunchKernelGGL(g2_prepare_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g2, count, prep,
                        pst);
     return hipGetLastError();
@@ -2744,7 +2461,7 @@ hipError_t launch_g1_prepare(const uint8_t *g1, size_t count, uint32_t *keys, ui
     return hipGetLastError();
 }
 
-size_t g1_point_words(size_t shares) { return shares * (size_t)kPtWords; }
+size_t g1_point_words(size_t shares) { return shares * (sizeof(PtProj<Fp>) / 4); }
 
 hipError_t launch_lagrange(const uint32_t *idx, const uint32_t *offsets, size_t groups,
                            size_t total, uint8_t *coeffs, uint8_t *status, hipStream_t s) {
@@ -2798,7 +2515,7 @@ hipError_t launch_g1_base_mul_check(const uint32_t *tab, const uint8_t *tst, siz
 }
 
 size_t g2_point_table_words(size_t points) { return points * (size_t)kG2PtWords; }
-size_t g2_point_words(size_t shares) { return shares * (size_t)kPt2Words; }
+size_t g2_point_words(size_t shares) { return shares * (sizeof(PtProj<Fp2>) / 4); }
 
 hipError_t launch_g2_points(const uint8_t *g2, size_t count, uint32_t *tab, uint8_t *gst,
                             hipStream_t s) {

@@ -331,11 +331,16 @@ def _verify_grouped(ciphertexts, shares, device, wire=False):
     return ok.cpu().tolist(), order, sprep
 
 
+def _combine_workspace(g2, total_shares, groups, device):
+    torch = _torch()
+    size = lib().hbrbc_g2_combine_workspace_size if g2 else lib().hbrbc_g1_combine_workspace_size
+    return torch.empty(max(size(total_shares, groups), 1), dtype=torch.uint8,
+                       device="cuda:%d" % device)
+
+
 def combine_workspace(total_shares, groups, device=0):
     """Device workspace for combining `total_shares` shares in `groups` groups."""
-    torch = _torch()
-    n = lib().hbrbc_g1_combine_workspace_size(total_shares, groups)
-    return torch.empty(max(n, 1), dtype=torch.uint8, device="cuda:%d" % device)
+    return _combine_workspace(False, total_shares, groups, device)
 
 
 def _ragged(offsets, *per_share):
@@ -368,11 +373,40 @@ def lagrange_coeffs(idx, offsets, stream=None):
     return coeffs, st
 
 
-def _combine_outputs(groups, device):
+def _combine_prepared(g2, lagrange, tab, count, rows, coef, offsets, ws, stream):
+    """The body of the four prepared combines, over the G1 table (g1_prepare)
+    or, with g2, the G2 table (g2_points_prepare) `tab` of exactly `count`
+    points; `coef` is per share: the caller's scalars or, with lagrange, the
+    node indices.  Returns (uncompressed, compressed, [parity,] status)."""
     torch = _torch()
-    return (torch.empty((groups, G1_BYTES), dtype=torch.uint8, device=device),
-            torch.empty((groups, G1_COMPRESSED_BYTES), dtype=torch.uint8, device=device),
-            torch.empty((groups,), dtype=torch.uint8, device=device))
+    L = lib()
+    if g2:
+        entry = L.hbrbc_sig_combine_prepared if lagrange else L.hbrbc_g2_lincomb_prepared
+    else:
+        entry = L.hbrbc_decrypt_combine_prepared if lagrange else L.hbrbc_g1_lincomb_prepared
+    table_size, ws_size, width = ((L.hbrbc_g2_points_size, L.hbrbc_g2_combine_workspace_size,
+                                   G2_BYTES) if g2 else
+                                  (L.hbrbc_g1_prepared_size, L.hbrbc_g1_combine_workspace_size,
+                                   G1_BYTES))
+    assert tab.numel() == table_size(count)
+    assert rows.dtype == torch.int32 and rows.dim() == 1
+    if lagrange:
+        assert coef.dtype == torch.int32 and coef.dim() == 1
+    else:
+        assert coef.dtype == torch.uint8 and coef.shape == (rows.shape[0], FR_BYTES)
+    groups, total = _ragged(offsets, rows, coef)
+    dev = rows.device
+    assert tab.device == dev
+    # the encodings, G2's parity byte, the status
+    outs = [torch.empty(shape, dtype=torch.uint8, device=dev)
+            for shape in [(groups, width), (groups, width // 2)] + [(groups,)] * (2 if g2 else 1)]
+    if ws is None:
+        ws = _combine_workspace(g2, total, groups, dev.index)
+    assert ws.numel() >= ws_size(total, groups)
+    _check(entry(
+        tab.data_ptr(), count, rows.data_ptr(), coef.data_ptr(), offsets.data_ptr(), groups,
+        *[o.data_ptr() for o in outs], ws.data_ptr(), _stream(dev, stream)))
+    return tuple(outs)
 
 
 def g1_lincomb_prepared(a_prep, prepared_count, rows, scalars, offsets, ws=None, stream=None):
@@ -381,21 +415,8 @@ def g1_lincomb_prepared(a_prep, prepared_count, rows, scalars, offsets, ws=None,
     [total, 32] (big-endian, < r), offsets int32 [groups + 1].  Returns (out96
     uint8 [groups, 96], out48 uint8 [groups, 48] compressed, status uint8
     [groups]: 0 ok, 1 infinity, 2 invalid input; failed groups are zero bytes)."""
-    torch = _torch()
-    assert a_prep.numel() == lib().hbrbc_g1_prepared_size(prepared_count)
-    assert rows.dtype == torch.int32 and rows.dim() == 1
-    assert scalars.dtype == torch.uint8 and scalars.shape == (rows.shape[0], FR_BYTES)
-    groups, total = _ragged(offsets, rows, scalars)
-    assert a_prep.device == rows.device
-    out96, out48, st = _combine_outputs(groups, rows.device)
-    if ws is None:
-        ws = combine_workspace(total, groups, rows.device.index)
-    assert ws.numel() >= lib().hbrbc_g1_combine_workspace_size(total, groups)
-    _check(lib().hbrbc_g1_lincomb_prepared(
-        a_prep.data_ptr(), prepared_count, rows.data_ptr(), scalars.data_ptr(), offsets.data_ptr(),
-        groups, out96.data_ptr(), out48.data_ptr(), st.data_ptr(), ws.data_ptr(),
-        _stream(rows.device, stream)))
-    return out96, out48, st
+    return _combine_prepared(False, False, a_prep, prepared_count, rows, scalars, offsets, ws,
+                             stream)
 
 
 def decrypt_combine_prepared(a_prep, prepared_count, rows, idx, offsets, ws=None, stream=None):
@@ -404,21 +425,7 @@ def decrypt_combine_prepared(a_prep, prepared_count, rows, idx, offsets, ws=None
     points) and comes from node idx[j]; rows, idx int32 [total], offsets int32
     [groups + 1].  Returns (out96, out48, status) as g1_lincomb_prepared, with
     status 3 for a group that repeats an index."""
-    torch = _torch()
-    assert a_prep.numel() == lib().hbrbc_g1_prepared_size(prepared_count)
-    assert rows.dtype == torch.int32 and rows.dim() == 1
-    assert idx.dtype == torch.int32 and idx.dim() == 1
-    groups, total = _ragged(offsets, rows, idx)
-    assert a_prep.device == rows.device
-    out96, out48, st = _combine_outputs(groups, rows.device)
-    if ws is None:
-        ws = combine_workspace(total, groups, rows.device.index)
-    assert ws.numel() >= lib().hbrbc_g1_combine_workspace_size(total, groups)
-    _check(lib().hbrbc_decrypt_combine_prepared(
-        a_prep.data_ptr(), prepared_count, rows.data_ptr(), idx.data_ptr(), offsets.data_ptr(),
-        groups, out96.data_ptr(), out48.data_ptr(), st.data_ptr(), ws.data_ptr(),
-        _stream(rows.device, stream)))
-    return out96, out48, st
+    return _combine_prepared(False, True, a_prep, prepared_count, rows, idx, offsets, ws, stream)
 
 
 def _u32_tensor(values, dev):
@@ -604,17 +611,7 @@ def sig_check_prepared(sig_tab, sig_count, keys, key_points, idx_key, prep, poin
 
 def combine_g2_workspace(total_shares, groups, device=0):
     """Device workspace for combining `total_shares` G2 shares in `groups` groups."""
-    torch = _torch()
-    n = lib().hbrbc_g2_combine_workspace_size(total_shares, groups)
-    return torch.empty(max(n, 1), dtype=torch.uint8, device="cuda:%d" % device)
-
-
-def _g2_combine_outputs(groups, device):
-    torch = _torch()
-    return (torch.empty((groups, G2_BYTES), dtype=torch.uint8, device=device),
-            torch.empty((groups, G2_COMPRESSED_BYTES), dtype=torch.uint8, device=device),
-            torch.empty((groups,), dtype=torch.uint8, device=device),
-            torch.empty((groups,), dtype=torch.uint8, device=device))
+    return _combine_workspace(True, total_shares, groups, device)
 
 
 def g2_lincomb_prepared(sig_tab, sig_count, rows, scalars, offsets, ws=None, stream=None):
@@ -624,21 +621,7 @@ def g2_lincomb_prepared(sig_tab, sig_count, rows, scalars, offsets, ws=None, str
     Returns (out192 uint8 [groups, 192], out96 uint8 [groups, 96] compressed,
     parity uint8 [groups], status uint8 [groups]: 0 ok, 1 infinity, 2 invalid
     input; failed groups are zero bytes)."""
-    torch = _torch()
-    assert sig_tab.numel() == lib().hbrbc_g2_points_size(sig_count)
-    assert rows.dtype == torch.int32 and rows.dim() == 1
-    assert scalars.dtype == torch.uint8 and scalars.shape == (rows.shape[0], FR_BYTES)
-    groups, total = _ragged(offsets, rows, scalars)
-    assert sig_tab.device == rows.device
-    out192, out96, par, st = _g2_combine_outputs(groups, rows.device)
-    if ws is None:
-        ws = combine_g2_workspace(total, groups, rows.device.index)
-    assert ws.numel() >= lib().hbrbc_g2_combine_workspace_size(total, groups)
-    _check(lib().hbrbc_g2_lincomb_prepared(
-        sig_tab.data_ptr(), sig_count, rows.data_ptr(), scalars.data_ptr(), offsets.data_ptr(),
-        groups, out192.data_ptr(), out96.data_ptr(), par.data_ptr(), st.data_ptr(), ws.data_ptr(),
-        _stream(rows.device, stream)))
-    return out192, out96, par, st
+    return _combine_prepared(True, False, sig_tab, sig_count, rows, scalars, offsets, ws, stream)
 
 
 def sig_combine_prepared(sig_tab, sig_count, rows, idx, offsets, ws=None, stream=None):
@@ -647,21 +630,7 @@ def sig_combine_prepared(sig_tab, sig_count, rows, idx, offsets, ws=None, stream
     comes from node idx[j]; rows, idx int32 [total], offsets int32 [groups +
     1].  Returns (out192, out96, parity, status) as g2_lincomb_prepared, with
     status 3 for a group that repeats an index."""
-    torch = _torch()
-    assert sig_tab.numel() == lib().hbrbc_g2_points_size(sig_count)
-    assert rows.dtype == torch.int32 and rows.dim() == 1
-    assert idx.dtype == torch.int32 and idx.dim() == 1
-    groups, total = _ragged(offsets, rows, idx)
-    assert sig_tab.device == rows.device
-    out192, out96, par, st = _g2_combine_outputs(groups, rows.device)
-    if ws is None:
-        ws = combine_g2_workspace(total, groups, rows.device.index)
-    assert ws.numel() >= lib().hbrbc_g2_combine_workspace_size(total, groups)
-    _check(lib().hbrbc_sig_combine_prepared(
-        sig_tab.data_ptr(), sig_count, rows.data_ptr(), idx.data_ptr(), offsets.data_ptr(),
-        groups, out192.data_ptr(), out96.data_ptr(), par.data_ptr(), st.data_ptr(), ws.data_ptr(),
-        _stream(rows.device, stream)))
-    return out192, out96, par, st
+    return _combine_prepared(True, True, sig_tab, sig_count, rows, idx, offsets, ws, stream)
 
 
 def _sig_results(out192, out96, par, st):

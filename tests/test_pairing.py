@@ -205,7 +205,7 @@ def test_prepared_checks_match_plain_checks():
 
 def test_g2_prepare_across_blocks():
     """The G2 preparation checks a point's order (block 2j) and computes its
-    lines (block 2j + 1) in different waves (HB_G2_SPLIT): 130 points, so
+    lines (block 2j + 1) in different waves: 130 points, so
     three block pairs and a ragged last one, with an off-curve, an
     off-subgroup and an infinity point at the block edges (63, 64, 129) and
     valid points elsewhere.  Prepared checks give exactly the plain checks'

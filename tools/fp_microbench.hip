@@ -188,8 +188,8 @@ __global__ __launch_bounds__(kMbBlock) __attribute__((amdgpu_waves_per_eu(2, 2))
     seed_fp(yc, g + 11);
     for (int it = 0; it < iters; ++it) {
         miller_sqr(f);
-        HB_APPLY_PREPARED(f, line + (it & 63) * kLineWords, xa, ya);
-        HB_APPLY_PREPARED(f, line + ((it + 7) & 63) * kLineWords, xc, yc);
+        apply_prepared_in(f, line + (it & 63) * kLineWords, xa, ya);
+        apply_prepared_in(f, line + ((it + 7) & 63) * kLineWords, xc, yc);
     }
     out[g] = fold12(f);
 }

@@ -18,8 +18,8 @@ before anything is timed:
 The checks are the valid-point shares of the epoch of
 tests/golden/sign_vectors.json (true ones, a tampered one, a stranger's key),
 64 per document; the groups are its 22-share group `cfg3_a` replicated, each
-on table rows of its own.  --combine-only runs (d) alone (the HB_G2_GLV A/B:
-HBRBC_LIB picks the library).  Per-kernel times come from a kernel trace taken
+on table rows of its own.  --combine-only runs (d) alone (for an A/B of two
+libraries: HBRBC_LIB picks the library).  Per-kernel times come from a kernel trace taken
 in a run of its own, as for tools/combine_bench.py (--kernel-stats).  Register
 and scratch sizes are read from the code object inside libhbrbc.so.  Writes
 profiles/threshold_sign.json and prints it as one JSON line."""
