@@ -173,6 +173,11 @@ def lib():
         "hbrbc_g1_poly_eval_prepared": (ctypes.c_int, [_P, _S, _P, _P, _S, _P, _P, _S, _P, _P, _P,
                                                        _P, _P]),
         "hbrbc_g1_base_mul_check": (ctypes.c_int, [_P, _S, _P, _P, _S, _P, _P]),
+        "hbrbc_g1_base_mul": (ctypes.c_int, [_P, _S, _P, _P, _P, _P, _P]),
+        "hbrbc_g1_mul_prepared": (ctypes.c_int, [_P, _S, _P, _P, _S, _P, _S, _P, _P, _P, _P, _P]),
+        "hbrbc_g2_mul_prepared": (ctypes.c_int, [_P, _S, _P, _P, _S, _P, _S, _P, _P, _P, _P, _P]),
+        "hbrbc_fr_poly_eval": (ctypes.c_int, [_P, _S, _P, _P, _S, _P, _P, _S, _P, _P, _P]),
+        "hbrbc_fr_dot": (ctypes.c_int, [_P, _P, _P, _S, _S, _P, _P, _P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -2736,6 +2736,85 @@ int hbrbc_sig_combine(const uint8_t *shares, const uint32_t *idx, size_t n, uint
     return HBRBC_OK;
 }
 
+// ---- share creation (pairing.hip): multiplications with a result, Fr --------
+// the status bytes of a g1_prepare table sit behind the coordinates of the
+// count it was prepared with
+static uint8_t *g1_prepared_status(void *table, size_t count) {
+    return static_cast<uint8_t *>(table) + round_up(g1_key_words(count) * 4, 256);
+}
+
+int hbrbc_g1_base_mul(const uint8_t *scalars, size_t count, void *out_table, uint8_t *out96,
+                      uint8_t *out48, uint8_t *status_out, void *stream) {
+    if (count == 0) return HBRBC_OK;
+    if (!scalars || !out_table || !status_out) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_g1_base_mul(scalars, count, static_cast<uint32_t *>(out_table),
+                              g1_prepared_status(out_table, count), out96, out48, status_out,
+                              static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
+int hbrbc_g1_mul_prepared(const void *a_prepared, size_t prepared_count, const int32_t *rows,
+                          const uint8_t *scalars, size_t nscalars, const int32_t *sidx,
+                          size_t count, void *out_table, uint8_t *out96, uint8_t *out48,
+                          uint8_t *status_out, void *stream) {
+    if (count == 0) return HBRBC_OK;
+    if (!a_prepared || !rows || !scalars || !out_table || !status_out)
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (!sidx && nscalars < count)
+        return fail(HBRBC_E_INVALID_ARG, "without sidx every result needs a scalar of its own");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_g1_mul_table(static_cast<const uint32_t *>(a_prepared),
+                               g1_prepared_status(const_cast<void *>(a_prepared), prepared_count),
+                               prepared_count, rows, scalars, nscalars, sidx, count,
+                               static_cast<uint32_t *>(out_table),
+                               g1_prepared_status(out_table, count), out96, out48, status_out,
+                               static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
+int hbrbc_g2_mul_prepared(const void *table, size_t table_count, const int32_t *rows,
+                          const uint8_t *scalars, size_t nscalars, const int32_t *sidx,
+                          size_t count, void *out_table, uint8_t *out192, uint8_t *out96,
+                          uint8_t *status_out, void *stream) {
+    if (count == 0) return HBRBC_OK;
+    if (!table || !rows || !scalars || !out_table || !status_out)
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (!sidx && nscalars < count)
+        return fail(HBRBC_E_INVALID_ARG, "without sidx every result needs a scalar of its own");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_g2_mul_table(static_cast<const uint32_t *>(table),
+                               g2_points_status(table, table_count), table_count, rows, scalars,
+                               nscalars, sidx, count, static_cast<uint32_t *>(out_table),
+                               const_cast<uint8_t *>(g2_points_status(out_table, count)), out192,
+                               out96, status_out, static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
+int hbrbc_fr_poly_eval(const uint8_t *scalars, size_t nscalars, const int32_t *rows,
+                       const uint32_t *offsets, size_t polys, const int32_t *poly,
+                       const uint32_t *x, size_t evals, uint8_t *out, uint8_t *status_out,
+                       void *stream) {
+    if (evals == 0) return HBRBC_OK;
+    if (!scalars || !rows || !offsets || !poly || !x || !out || !status_out)
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_fr_horner(scalars, nscalars, rows, offsets, polys, poly, x, evals, out,
+                            status_out, static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
+int hbrbc_fr_dot(const uint8_t *a, const uint8_t *b, const uint32_t *offsets, size_t groups,
+                 size_t total, uint8_t *out, uint8_t *status_out, void *stream) {
+    if (groups == 0) return HBRBC_OK;
+    if (!offsets || !out || !status_out || (total && (!a || !b)))
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_fr_dot(a, b, offsets, groups, total, out, status_out,
+                         static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
 // ---- f2: the Broadcast state machine, batched (sim.hip) -------------------
 size_t hbrbc_sm_state_bytes(size_t n, size_t roots) { return sm_state_bytes(n, roots); }
 

@@ -312,6 +312,27 @@ hipError_t launch_g2_reduce_encode(const uint32_t *ws, const uint8_t *pst, const
                                    size_t groups, size_t total, const uint8_t *lst,
                                    uint8_t *out192, uint8_t *out96, uint8_t *parity,
                                    uint8_t *status, hipStream_t s);
+// share creation (pairing.hip): [scalars[sidx[j]]] T[rows[j]] over a g1_prepare
+// / g2_points table and [s] G1::one(), results in table form (otab, ost) and
+// optionally encoded; ragged Fr polynomials evaluated at 32-bit integers and
+// ragged Fr dot products, 32 big-endian bytes per scalar
+hipError_t launch_g1_mul_table(const uint32_t *tab, const uint8_t *tst, size_t nprep,
+                               const int32_t *rows, const uint8_t *scalars, size_t nscalars,
+                               const int32_t *sidx, size_t count, uint32_t *otab, uint8_t *ost,
+                               uint8_t *out96, uint8_t *out48, uint8_t *status, hipStream_t s);
+hipError_t launch_g2_mul_table(const uint32_t *tab, const uint8_t *tst, size_t nprep,
+                               const int32_t *rows, const uint8_t *scalars, size_t nscalars,
+                               const int32_t *sidx, size_t count, uint32_t *otab, uint8_t *ost,
+                               uint8_t *out192, uint8_t *out96, uint8_t *status, hipStream_t s);
+hipError_t launch_g1_base_mul(const uint8_t *scalars, size_t count, uint32_t *otab, uint8_t *ost,
+                              uint8_t *out96, uint8_t *out48, uint8_t *status, hipStream_t s);
+hipError_t launch_fr_horner(const uint8_t *scalars, size_t nscalars, const int32_t *rows,
+                            const uint32_t *offsets, size_t polys, const int32_t *poly,
+                            const uint32_t *x, size_t evals, uint8_t *out, uint8_t *status,
+                            hipStream_t s);
+hipError_t launch_fr_dot(const uint8_t *a, const uint8_t *b, const uint32_t *offsets,
+                         size_t groups, size_t total, uint8_t *out, uint8_t *status,
+                         hipStream_t s);
 // compressed wire encodings (pairing.hip): the g1_prepare / g2_points tables
 // from 48- / 96-byte points, and compressed to uncompressed bytes with a
 // status byte per point (0 ok, 1 infinity, 2 invalid)

@@ -2115,6 +2115,273 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kPai
     status[g] = (uint8_t)st;
 }
 
+// ------------------------------------------------------------ share creation
+// What a node does to send: `decrypt_share_no_verify` ([sk_i] U,
+// threshold_decrypt.rs:161), `sign_g2` ([sk_i] H, threshold_sign.rs:167), the
+// dealer's `BivarPoly::commitment()` and `SecretKeyShare::public_key_share`
+// ([s] G1::one()), and SyncKeyGen's Fr side: `our_part.row(i + 1)`
+// (sync_key_gen.rs:413-417), `row.evaluate(idx + 1)` (:459) and the
+// interpolation of `generate` (:523-524).  The multiplications are the GLV
+// loops above with the result kept on the device: one inversion per lane, the
+// affine point written as an entry of a g1_prepare / g2_points table (bit for
+// bit what the decoders give for the result's bytes: every field operation
+// returns the canonical representative, and a product of a checked point stays
+// in the order-r subgroup, so no second check is due) and, where asked, in the
+// wire encodings.  The loops branch on scalar bits: not constant-time, meant
+// for simulations and test networks that hold every node's secrets anyway.
+
+// The G2 twin of g1_affine_encode: Montgomery affine (xm, ym), zero for
+// infinity, and the encodings into zeroed buffers where the pointers are
+// non-null (no parity byte: a share is not a signature).
+DEV int g2_affine_encode_pt(const PtProj<Fp2> &acc, Fp2 &xm, Fp2 &ym, uint8_t *o192,
+                            uint8_t *o96) {
+    if (fp2_is_zero(acc.z)) {
+        fp2_zero(xm);
+        fp2_zero(ym);
+        if (o192) o192[0] = 0x40;
+        if (o96) o96[0] = 0xC0;
+        return CB_INF;
+    }
+    Fp2 zi, x, y;
+    fp2_inv(zi, acc.z);
+    fp2_mul(xm, acc.x, zi);
+    fp2_mul(ym, acc.y, zi);
+    if (!o192 && !o96) return CB_OK;
+    fp2_from_mont(x, xm);
+    fp2_from_mont(y, ym);
+    if (o192) g2_store_be192(o192, x, y);
+    if (o96) {
+        int cmp = fp_cmp_neg(y.c1);
+        if (cmp == 0) cmp = fp_cmp_neg(y.c0);
+        store_be48_raw(o96, x.c1, (uint8_t)(0x80 | (cmp > 0 ? 0x20 : 0)));
+        store_be48_raw(o96 + 48, x.c0, 0);
+    }
+    return CB_OK;
+}
+
+DEV int pt_affine_encode(const PtProj<Fp> &acc, Fp &xm, Fp &ym, uint8_t *ou, uint8_t *oc) {
+    return g1_affine_encode(acc, xm, ym, ou, oc);
+}
+DEV int pt_affine_encode(const PtProj<Fp2> &acc, Fp2 &xm, Fp2 &ym, uint8_t *ou, uint8_t *oc) {
+    return g2_affine_encode_pt(acc, xm, ym, ou, oc);
+}
+
+// The tail of the three multiplication kernels: result j (acc, unless st is
+// PT_BAD) as entry j of the output table with its status byte, and in the
+// uncompressed (2 sizeof(F) bytes) and compressed (sizeof(F) bytes) encodings
+// where the pointers are non-null; zero bytes for PT_BAD.
+template <class F>
+DEV void store_result(const PtProj<F> &acc, int st, size_t j, uint32_t *otab, uint8_t *ost,
+                      uint8_t *out_u, uint8_t *out_c, uint8_t *status) {
+    constexpr int kU = 2 * (int)sizeof(F), kC = (int)sizeof(F);
+    uint8_t *ou = out_u ? out_u + (size_t)kU * j : nullptr;
+    uint8_t *oc = out_c ? out_c + (size_t)kC * j : nullptr;
+    if (ou)
+        for (int i = 0; i < kU; ++i) ou[i] = 0;
+    if (oc)
+        for (int i = 0; i < kC; ++i) oc[i] = 0;
+    F xm, ym;
+    if (st != PT_BAD) {
+        st = pt_affine_encode(acc, xm, ym, ou, oc);   // CB_OK / CB_INF = PT_OK / PT_INF
+    } else {
+        fe_zero(xm);
+        fe_zero(ym);
+    }
+    store_affine(otab + j * (2 * sizeof(F) / 4), xm, ym);
+    ost[j] = (uint8_t)st;
+    status[j] = (uint8_t)st;
+}
+
+// The body of the two variable-base kernels, one lane per result j:
+// [scalars[sidx[j]]] T[rows[j]] (sidx null: scalar j) over a g1_prepare /
+// g2_points table of `nprep` points.  A zero scalar and an entry at infinity
+// give infinity (status 1); an invalid entry, a row outside the table, an
+// sidx outside [0, nscalars) and a scalar >= r give status 2 -- an index out
+// of range is never a read out of range.  Lanes of a wave that share a scalar
+// share their GLV digits, so the branch on the digit and the operand select
+// of pt_mul_glv are uniform for the wave.
+template <class F>
+DEV void mul_table(const uint32_t *tab, const uint8_t *tst, size_t nprep, const int32_t *rows,
+                   const uint8_t *scalars, size_t nscalars, const int32_t *sidx, size_t count,
+                   uint32_t *otab, uint8_t *ost, uint8_t *out_u, uint8_t *out_c,
+                   uint8_t *status) {
+    const size_t j = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (j >= count) return;
+    const int32_t row = rows[j];
+    int st = (row >= 0 && (size_t)row < nprep) ? tst[row] : PT_BAD;
+    const int64_t si = sidx ? (int64_t)sidx[j] : (int64_t)j;
+    Fr k;
+    if (si >= 0 && (uint64_t)si < nscalars) {
+        fr_load_be32(k, scalars + 32 * (size_t)si);
+        if (!fr_is_canonical(k)) st = PT_BAD;
+    } else {
+        st = PT_BAD;
+    }
+    PtProj<F> acc;
+    if (st == PT_OK) {
+        F x, y;
+        load_affine(tab + (size_t)row * (2 * sizeof(F) / 4), x, y);
+        pt_mul_glv(acc, x, y, k);
+    } else {
+        pt_identity(acc);
+    }
+    store_result(acc, st, j, otab, ost, out_u, out_c, status);
+}
+
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kG1PrepWpe, kG1PrepWpe))) void g1_mul_table_kernel(
+    const uint32_t *__restrict__ tab, const uint8_t *__restrict__ tst, size_t nprep,
+    const int32_t *__restrict__ rows, const uint8_t *__restrict__ scalars, size_t nscalars,
+    const int32_t *__restrict__ sidx, size_t count, uint32_t *__restrict__ otab,
+    uint8_t *__restrict__ ost, uint8_t *__restrict__ out96, uint8_t *__restrict__ out48,
+    uint8_t *__restrict__ status) {
+    mul_table<Fp>(tab, tst, nprep, rows, scalars, nscalars, sidx, count, otab, ost, out96, out48,
+                  status);
+}
+
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kPairWpe, kPairWpe))) void g2_mul_table_kernel(
+    const uint32_t *__restrict__ tab, const uint8_t *__restrict__ tst, size_t nprep,
+    const int32_t *__restrict__ rows, const uint8_t *__restrict__ scalars, size_t nscalars,
+    const int32_t *__restrict__ sidx, size_t count, uint32_t *__restrict__ otab,
+    uint8_t *__restrict__ ost, uint8_t *__restrict__ out192, uint8_t *__restrict__ out96,
+    uint8_t *__restrict__ status) {
+    mul_table<Fp2>(tab, tst, nprep, rows, scalars, nscalars, sidx, count, otab, ost, out192,
+                   out96, status);
+}
+
+// Kernel: one lane per result [s_i] G1::one(), the GLV loop of
+// g1_base_mul_check_kernel (the generator, [x^2] G and their sum as affine
+// constants through the mixed addition) with the result written as
+// g1_horner_kernel writes its own.  s = 0 gives infinity (status 1), s >= r
+// status 2.
+__global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kG1PrepWpe, kG1PrepWpe))) void g1_base_mul_kernel(
+    const uint8_t *__restrict__ scalars, size_t count, uint32_t *__restrict__ otab,
+    uint8_t *__restrict__ ost, uint8_t *__restrict__ out96, uint8_t *__restrict__ out48,
+    uint8_t *__restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (i >= count) return;
+    Fr k;
+    fr_load_be32(k, scalars + 32 * i);
+    const int st = fr_is_canonical(k) ? PT_OK : PT_BAD;
+    PtProj<Fp> acc;
+    pt_identity(acc);
+    if (st == PT_OK) {
+        uint64_t k1hi, k1lo, k2hi, k2lo;
+        glv_split(k, k1hi, k1lo, k2hi, k2lo);
+        for (int b = 127; b >= 0; --b) {
+            pt_dbl(acc);
+            const unsigned sel = glv_digit(k1hi, k1lo, k2hi, k2lo);
+            if (sel) {
+                Fp ox, oy;
+#pragma unroll
+                for (int w = 0; w < NL; ++w) {
+                    ox.l[w] = sel == 1 ? kG1GenX[w] : (sel == 2 ? kG1GenQX[w] : kG1GenTX[w]);
+                    oy.l[w] = sel == 1 ? kG1GenY[w] : (sel == 2 ? kG1GenNegY[w] : kG1GenTY[w]);
+                }
+                pt_add_affine(acc, ox, oy);
+            }
+        }
+    }
+    store_result(acc, st, i, otab, ost, out96, out48, status);
+}
+
+DEV void fr_zero(Fr &r) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i) r.l[i] = 0;
+}
+
+// a + b mod r for a, b < r (the sum stays below 2^256)
+DEV void fr_add(Fr &r, const Fr &a, const Fr &b) {
+    uint32_t t[NR], s[NR];
+    uint32_t c = 0, br = 0;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) t[i] = addc(a.l[i], b.l[i], c, &c);
+#pragma unroll
+    for (int i = 0; i < NR; ++i) s[i] = subb(t[i], kFrR[i], br, &br);
+#pragma unroll
+    for (int i = 0; i < NR; ++i) r.l[i] = br ? t[i] : s[i];
+}
+
+// Kernel: the Fr twin of g1_horner_kernel, one lane per evaluation e of
+// polynomial poly[e] at the raw 32-bit x[e].  Polynomial p has the
+// coefficients scalars[rows[offsets[p] .. offsets[p + 1])] (32 big-endian
+// bytes each, constant term first), ranges clamped to offsets[polys].
+// Horner's rule on canonical values: acc <- acc x + c with x in Montgomery
+// form, so the Montgomery product returns the canonical acc x.  x = 0 gives
+// the constant term, the empty polynomial 0.  A coefficient >= r, a row
+// outside [0, nscalars) or a poly outside [0, polys): status 2, zero bytes.
+__global__ __launch_bounds__(kPairBlock) void fr_horner_kernel(
+    const uint8_t *__restrict__ scalars, size_t nscalars, const int32_t *__restrict__ rows,
+    const uint32_t *__restrict__ offsets, size_t polys, const int32_t *__restrict__ poly,
+    const uint32_t *__restrict__ xs, size_t evals, uint8_t *__restrict__ out,
+    uint8_t *__restrict__ status) {
+    const size_t e = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (e >= evals) return;
+    const int32_t p = poly[e];
+    int st = PT_OK;
+    size_t b = 0, en = 0;
+    if (p >= 0 && (size_t)p < polys)
+        group_range(offsets, (size_t)p, offsets[polys], b, en);
+    else
+        st = PT_BAD;
+    Fr xm, acc;
+    fr_from_u64(xm, xs[e]);
+    fr_zero(acc);
+    for (size_t k = en; k > b && st == PT_OK; --k) {
+        const int32_t row = rows[k - 1];
+        Fr c;
+        if (row < 0 || (size_t)row >= nscalars) {
+            st = PT_BAD;   // a row past the scalars is an invalid input, never a read
+            break;
+        }
+        fr_load_be32(c, scalars + 32 * (size_t)row);
+        if (!fr_is_canonical(c)) st = PT_BAD;
+        fr_mul(acc, acc, xm);
+        fr_add(acc, acc, c);
+    }
+    if (st != PT_OK) fr_zero(acc);
+    fr_store_be32(out + 32 * e, acc);
+    status[e] = (uint8_t)st;
+}
+
+// Kernel: one lane per group g, sum_j a_j b_j mod r over j in [offsets[g],
+// offsets[g + 1]) clamped to `total` (32 big-endian bytes per operand).  The
+// Montgomery products carry a factor 2^-256 each, their sum one product with
+// 2^512 takes out.  An operand >= r: status 2, zero bytes; an empty group is 0.
+// With the coefficients of lagrange_kernel this is the
+// `Poly::interpolate(..).evaluate(0)` of `generate`.
+__global__ __launch_bounds__(kPairBlock) void fr_dot_kernel(
+    const uint8_t *__restrict__ a, const uint8_t *__restrict__ bb,
+    const uint32_t *__restrict__ offsets, size_t groups, size_t total,
+    uint8_t *__restrict__ out, uint8_t *__restrict__ status) {
+    const size_t g = (size_t)blockIdx.x * kPairBlock + threadIdx.x;
+    if (g >= groups) return;
+    size_t b, e;
+    group_range(offsets, g, total, b, e);
+    int st = PT_OK;
+    Fr acc;
+    fr_zero(acc);
+    for (size_t j = b; j < e; ++j) {
+        Fr x, y;
+        fr_load_be32(x, a + 32 * j);
+        fr_load_be32(y, bb + 32 * j);
+        if (!fr_is_canonical(x) || !fr_is_canonical(y)) {
+            st = PT_BAD;
+            break;
+        }
+        fr_mul(x, x, y);
+        fr_add(acc, acc, x);
+    }
+    if (st == PT_OK) {
+        Fr r2;
+        fr_set(r2, kFrR2);
+        fr_mul(acc, acc, r2);
+    } else {
+        fr_zero(acc);
+    }
+    fr_store_be32(out + 32 * g, acc);
+    status[g] = (uint8_t)st;
+}
+
 // ------------------------------------------------- compressed encodings
 // hbbft's messages carry every point in the crate's compressed form: 48 bytes
 // for G1 (DecryptionShare, PublicKeyShare, a ciphertext's U), 96 for G2
@@ -2556,6 +2823,58 @@ hipError_t launch_g2_reduce_encode(const uint32_t *ws, const uint8_t *pst, const
     const unsigned blocks = (unsigned)((groups + kPairBlock - 1) / kPairBlock);
     hipLaunchKernelGGL(g2_reduce_encode_kernel, dim3(blocks), dim3(kPairBlock), 0, s, ws, pst,
                        offsets, groups, total, lst, out192, out96, parity, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_g1_mul_table(const uint32_t *tab, const uint8_t *tst, size_t nprep,
+                               const int32_t *rows, const uint8_t *scalars, size_t nscalars,
+                               const int32_t *sidx, size_t count, uint32_t *otab, uint8_t *ost,
+                               uint8_t *out96, uint8_t *out48, uint8_t *status, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g1_mul_table_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab, tst, nprep,
+                       rows, scalars, nscalars, sidx, count, otab, ost, out96, out48, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_g2_mul_table(const uint32_t *tab, const uint8_t *tst, size_t nprep,
+                               const int32_t *rows, const uint8_t *scalars, size_t nscalars,
+                               const int32_t *sidx, size_t count, uint32_t *otab, uint8_t *ost,
+                               uint8_t *out192, uint8_t *out96, uint8_t *status, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g2_mul_table_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab, tst, nprep,
+                       rows, scalars, nscalars, sidx, count, otab, ost, out192, out96, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_g1_base_mul(const uint8_t *scalars, size_t count, uint32_t *otab, uint8_t *ost,
+                              uint8_t *out96, uint8_t *out48, uint8_t *status, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g1_base_mul_kernel, dim3(blocks), dim3(kPairBlock), 0, s, scalars, count,
+                       otab, ost, out96, out48, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_fr_horner(const uint8_t *scalars, size_t nscalars, const int32_t *rows,
+                            const uint32_t *offsets, size_t polys, const int32_t *poly,
+                            const uint32_t *x, size_t evals, uint8_t *out, uint8_t *status,
+                            hipStream_t s) {
+    if (evals == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((evals + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(fr_horner_kernel, dim3(blocks), dim3(kPairBlock), 0, s, scalars, nscalars,
+                       rows, offsets, polys, poly, x, evals, out, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_fr_dot(const uint8_t *a, const uint8_t *b, const uint32_t *offsets,
+                         size_t groups, size_t total, uint8_t *out, uint8_t *status,
+                         hipStream_t s) {
+    if (groups == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((groups + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(fr_dot_kernel, dim3(blocks), dim3(kPairBlock), 0, s, a, b, offsets, groups,
+                       total, out, status);
     return hipGetLastError();
 }
 

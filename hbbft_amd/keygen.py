@@ -26,10 +26,20 @@ fixed-base comparisons: `hbrbc_g1_poly_eval_prepared` (Horner's rule, one lane
 per evaluation, results in g1_prepare table form so they feed the next step on
 the device) and `hbrbc_g1_base_mul_check` (hbbft_amd/csrc/pairing.hip).
 
-Decrypting rows and values stays with the caller: `sec_key.decrypt` (:564-567,
-:596-599) includes xor_with_hash, a ChaCha stream; the functions here take the
-decrypted Fr scalars as 32 big-endian bytes.  So does the secret half of
-`generate` (`Poly::interpolate` in Fr, :523-524), like share creation.
+The sending side is here too, for a simulator or test network that hosts
+every node: `base_mul` ([s] G1::one() with a result: `BivarPoly::commitment`,
+`public_key_share`), `fr_poly_eval` (`BivarPoly::row`, `Poly::evaluate`) and
+`fr_dot` (with the Lagrange coefficients: the `Poly::interpolate(..)
+.evaluate(0)` of `generate`, :523-524) carry `generate_part` (:413-417),
+`ack_values` (:459), `secret_key_share` and `sync_key_gen_network`, an honest
+N-node run whose secret key shares feed threshold.create_decryption_shares /
+create_signature_shares.  These kernels branch on scalar bits: they are not
+constant-time.
+
+Encrypting and decrypting rows and values stays with the caller:
+`sec_key.decrypt` (:564-567, :596-599) includes xor_with_hash, a ChaCha
+stream; the functions here take and return Fr scalars as 32 big-endian bytes.
+So does `BivarPoly::random`.
 Commitment points arrive compressed (48 bytes), as the messages carry them.
 Functions that take node indices form x = idx + 1 and raise ValueError for
 idx >= 0xFFFFFFFF.  There is no CPU fallback: without the library or a GPU
@@ -129,6 +139,82 @@ def base_mul_check(tab, prepared_count, rows, scalars, stream=None):
                                          scalars.data_ptr(), count, ok.data_ptr(),
                                          _stream(rows.device, stream)))
     return ok
+
+
+def base_mul(scalars, encode=True, stream=None):
+    """[s_i] G1::one() for scalars uint8 [count, 32] (big-endian, < r):
+    `Poly::commitment`, `BivarPoly::commitment`, `public_key_share`.  Returns
+    (table uint8 -- the results as a g1_prepare table of `count` points --,
+    out96 uint8 [count, 96], out48 uint8 [count, 48] (both None without
+    `encode`), status uint8 [count]: 0 ok, 1 infinity (s = 0), 2 s >= r).  Not
+    constant-time."""
+    torch = _torch()
+    assert scalars.dtype == torch.uint8 and scalars.dim() == 2 and scalars.shape[1] == FR_BYTES
+    assert scalars.is_contiguous()
+    _need_gpu()
+    count, dev = scalars.shape[0], scalars.device
+    out = torch.empty(max(1, lib().hbrbc_g1_prepared_size(count)), dtype=torch.uint8, device=dev)
+    o96 = o48 = None
+    if encode:
+        o96 = torch.empty((count, G1_BYTES), dtype=torch.uint8, device=dev)
+        o48 = torch.empty((count, G1_COMPRESSED_BYTES), dtype=torch.uint8, device=dev)
+    st = torch.empty((count,), dtype=torch.uint8, device=dev)
+    _check(lib().hbrbc_g1_base_mul(scalars.data_ptr(), count, out.data_ptr(),
+                                   o96.data_ptr() if encode else None,
+                                   o48.data_ptr() if encode else None, st.data_ptr(),
+                                   _stream(dev, stream)))
+    return out, o96, o48, st
+
+
+def fr_poly_eval(scalars, rows, offsets, poly, x, stream=None):
+    """poly_eval_prepared in the scalar field: polynomial p has the
+    coefficients scalars[rows[offsets[p] .. offsets[p + 1])], constant term
+    first (scalars uint8 [nscalars, 32], rows int32 [total], offsets int32
+    [polys + 1]); evaluation e is polynomial poly[e] at x[e] (int32 [evals],
+    x the bits of an unsigned 32-bit value).  Returns (out uint8 [evals, 32],
+    status uint8 [evals]: 0 ok, 2 a coefficient >= r, a row or poly index out
+    of range -- zero bytes)."""
+    torch = _torch()
+    assert scalars.dtype == torch.uint8 and scalars.dim() == 2 and scalars.shape[1] == FR_BYTES
+    assert scalars.is_contiguous()
+    assert rows.dtype == torch.int32 and rows.dim() == 1
+    polys, total = _ragged(offsets, rows)
+    assert poly.dtype == torch.int32 and poly.dim() == 1 and poly.is_contiguous()
+    assert x.dtype == torch.int32 and x.shape == poly.shape and x.is_contiguous()
+    assert scalars.device == rows.device == poly.device == x.device
+    _need_gpu()
+    evals, dev = poly.shape[0], rows.device
+    out = torch.empty((evals, FR_BYTES), dtype=torch.uint8, device=dev)
+    st = torch.empty((evals,), dtype=torch.uint8, device=dev)
+    if total == 0:   # only empty polynomials: the entry still wants a rows pointer
+        rows = torch.zeros(1, dtype=torch.int32, device=dev)
+    if scalars.shape[0] == 0:
+        scalars = torch.zeros((1, FR_BYTES), dtype=torch.uint8, device=dev)
+        nscalars = 0
+    else:
+        nscalars = scalars.shape[0]
+    _check(lib().hbrbc_fr_poly_eval(scalars.data_ptr(), nscalars, rows.data_ptr(),
+                                    offsets.data_ptr(), polys, poly.data_ptr(), x.data_ptr(),
+                                    evals, out.data_ptr(), st.data_ptr(), _stream(dev, stream)))
+    return out, st
+
+
+def fr_dot(a, b, offsets, stream=None):
+    """Per group sum_j a_j b_j mod r over ragged groups: a, b uint8 [total, 32],
+    offsets int32 [groups + 1].  Returns (out uint8 [groups, 32], status uint8
+    [groups]: 0 ok, 2 an operand >= r -- zero bytes).  With the coefficients of
+    threshold.lagrange_coeffs this interpolates at 0."""
+    torch = _torch()
+    for s in (a, b):
+        assert s.dtype == torch.uint8 and s.dim() == 2 and s.shape[1] == FR_BYTES
+    groups, total = _ragged(offsets, a, b)
+    _need_gpu()
+    dev = a.device
+    out = torch.empty((groups, FR_BYTES), dtype=torch.uint8, device=dev)
+    st = torch.empty((groups,), dtype=torch.uint8, device=dev)
+    _check(lib().hbrbc_fr_dot(a.data_ptr(), b.data_ptr(), offsets.data_ptr(), groups, total,
+                              out.data_ptr(), st.data_ptr(), _stream(dev, stream)))
+    return out, st
 
 
 def commitment_rows(commit_tab, commits, t, requests, stream=None):
@@ -350,3 +436,171 @@ def sync_key_gen_grouped(t, our_idx, parts, acks, n=None, device=0):
     ktab, o96, o48, st = _generate(t, ctab, len(parts), complete, dev)
     (stab, s96, s48, sst), pk = _key_shares(ktab, t + 1, n, dev)
     return part_ok, ack_ok, complete, _encodings(o96, o48, st), (stab, s96, s48, sst, pk)
+
+
+# ---- the sending side: the dealer's Part, the Acks, the secret key share ----
+def _bivar_rows(t, dpolys, nparts, n, dev):
+    """`BivarPoly::row(node + 1)` of `nparts` polynomials (dpolys uint8 [nparts
+    * commitment_len(t), 32]) for node < n: coefficient j of a row is the
+    polynomial over the entries (0..t, j), as commitment_rows builds it in G1.
+    Returns (uint8 [nparts * n * (t + 1), 32], part-major then node; status)."""
+    m = commitment_len(t)
+    rows = [p * m + coeff_pos(i, j) for p in range(nparts) for j in range(t + 1)
+            for i in range(t + 1)]
+    poly = [p * (t + 1) + j for p in range(nparts) for _ in range(n) for j in range(t + 1)]
+    xs = [node + 1 for _ in range(nparts) for node in range(n) for _ in range(t + 1)]
+    return fr_poly_eval(dpolys, _i32(rows, dev), _offsets([t + 1] * (nparts * (t + 1)), dev),
+                        _i32(poly, dev), _u32_tensor(xs, dev))
+
+
+def _row_values(t, drows, nrows, n, dev):
+    """`row.evaluate(idx + 1)` for idx < n of `nrows` rows of t + 1 scalars laid
+    end to end.  Returns (uint8 [nrows * n, 32], row-major; status)."""
+    poly = [r for r in range(nrows) for _ in range(n)]
+    xs = [idx + 1 for _ in range(nrows) for idx in range(n)]
+    return fr_poly_eval(drows, _i32(list(range(nrows * (t + 1))), dev),
+                        _offsets([t + 1] * nrows, dev), _i32(poly, dev), _u32_tensor(xs, dev))
+
+
+def _scalar_list(dev_scalars):
+    return [bytes(v) for v in dev_scalars.cpu().numpy()]
+
+
+def _all_ok(st, what):
+    if int(st.max()) != EVAL_OK:
+        raise ValueError("%s: a scalar is not below r" % what)
+
+
+def generate_part(t, poly, n, device=0):
+    """The dealer's half of a `Part` (sync_key_gen.rs:413-417): poly = the
+    commitment_len(t) coefficients of a symmetric `BivarPoly` of degree t in
+    coeff_pos order, 32 bytes each (`BivarPoly::random` stays with the caller,
+    like the encryption of the rows).  Returns (`our_part.commitment()` as
+    commitment_len(t) compressed points, `our_part.row(i + 1)` for i < n as n
+    lists of t + 1 scalars).  A coefficient >= r raises ValueError."""
+    if len(poly) != commitment_len(t):
+        raise ValueError("polynomial of %d coefficients, expected %d"
+                         % (len(poly), commitment_len(t)))
+    if not 0 < n < 0xFFFFFFFF:
+        raise ValueError("n = %r nodes" % (n,))
+    dev = "cuda:%d" % device
+    _need_gpu()
+    dpoly = _scalars(poly, dev, "coefficient")
+    _, _, c48, cst = base_mul(dpoly)
+    rows, rst = _bivar_rows(t, dpoly, 1, n, dev)
+    _all_ok(rst, "generate_part")
+    flat = _scalar_list(rows)
+    return ([bytes(v) for v in c48.cpu().numpy()],
+            [flat[i * (t + 1):(i + 1) * (t + 1)] for i in range(n)])
+
+
+def ack_values(row, n, device=0):
+    """The values of an `Ack` (sync_key_gen.rs:459): `row.evaluate(idx + 1)` for
+    idx < n of our decrypted row (scalars of 32 bytes, constant term first), to
+    be encrypted to node idx by the caller.  Returns n scalars."""
+    if not row:
+        raise ValueError("empty row")
+    if not 0 < n < 0xFFFFFFFF:
+        raise ValueError("n = %r nodes" % (n,))
+    dev = "cuda:%d" % device
+    _need_gpu()
+    vals, st = _row_values(len(row) - 1, _scalars(row, dev, "row coefficient"), 1, n, dev)
+    _all_ok(st, "ack_values")
+    return _scalar_list(vals)
+
+
+def _take(t, pairs):
+    """The first t + 1 (sender_idx, value) of a part in ascending sender, a
+    sender counting once: `part.values.iter().take(threshold + 1)` (:523) over
+    the BTreeMap that :606 fills (a repeated Ack returns at :588-590)."""
+    seen = {}
+    for s, v in pairs:
+        _x_of(s)
+        seen.setdefault(s, v)
+    return sorted(seen.items())[:t + 1]
+
+
+def _secret_key_shares(t, nodes, dev):
+    """sum over a node's parts of the interpolation at 0 of the part's pairs,
+    for every node of `nodes` = [values_by_part]: one Lagrange group per (node,
+    part), one dot product per node over all of its terms."""
+    from .threshold import lagrange_coeffs
+    idx, vals, lag, dot = [], [], [], []
+    for parts in nodes:
+        for pairs in parts:
+            pick = _take(t, pairs)
+            idx += [s for s, _ in pick]
+            vals += [v for _, v in pick]
+            lag.append(len(pick))
+        dot.append(len(idx) - sum(dot))
+    coeffs, _ = lagrange_coeffs(_u32_tensor(idx, dev), _offsets(lag, dev))
+    out, st = fr_dot(coeffs, _scalars(vals, dev, "value"), _offsets(dot, dev))
+    _all_ok(st, "secret_key_share")
+    return _scalar_list(out)
+
+
+def secret_key_share(t, values_by_part, device=0):
+    """The secret half of `generate` (sync_key_gen.rs:516-534): values_by_part
+    holds, per complete part, the (sender_idx, value) pairs that passed
+    handle_ack.  Per part the pairs are sorted by sender and the first t + 1
+    interpolated at 0 (x = sender_idx + 1; with fewer pairs what there is, as
+    the crate does), and the results summed: sk_i, 32 bytes.  No part gives
+    zero (`Fr::zero()`)."""
+    _need_gpu()
+    return _secret_key_shares(t, [values_by_part], "cuda:%d" % device)[0]
+
+
+def sync_key_gen_network(t, polys, device=0, ack_senders=None):
+    """An honest run of `SyncKeyGen` among N = len(polys) nodes hosted in one
+    process, from given polynomials (polys[p]: node p's `BivarPoly`, as for
+    generate_part): every commitment, row and Ack value is produced on the
+    device, every node checks every Part and every Ack through the checks of
+    check_parts / check_acks, and `generate` runs for every node.
+    ack_senders[p] lists the nodes whose Acks of part p are handled (default:
+    all N); a part is complete with more than 2t distinct ones.  Returns a
+    dict: commitments [p][k] 48 bytes, rows [p][node][j] and values
+    [p][sender][node] 32 bytes, part_ok [node][p] and ack_ok [node] (one
+    outcome per (p, sender) of ack_senders, in that order), complete, key_set
+    (generate_public's pairs), key_shares (public_key_shares' tuple: the pk_i
+    table first), secret_key_shares [node] 32 bytes."""
+    n = len(polys)
+    m = commitment_len(t)
+    if n == 0:
+        raise ValueError("no nodes")
+    for f in polys:
+        if len(f) != m:
+            raise ValueError("polynomial of %d coefficients, expected %d" % (len(f), m))
+    if ack_senders is None:
+        ack_senders = [list(range(n))] * n
+    if len(ack_senders) != n or any(not 0 <= s < n for a in ack_senders for s in a):
+        raise ValueError("ack_senders: one list of node indices per part")
+    _need_gpu()
+    dev = "cuda:%d" % device
+    dpolys = _scalars([c for f in polys for c in f], dev, "coefficient")
+    ctab, _, c48, cst = base_mul(dpolys)
+    _all_ok(cst, "commitment")
+    drows, rst = _bivar_rows(t, dpolys, n, n, dev)
+    _all_ok(rst, "rows")
+    dvals, vst = _row_values(t, drows, n * n, n, dev)
+    _all_ok(vst, "values")
+    c48h, rowh, valh = [bytes(v) for v in c48.cpu().numpy()], _scalar_list(drows), _scalar_list(dvals)
+    commitments = [c48h[p * m:(p + 1) * m] for p in range(n)]
+    rows = [[rowh[(p * n + i) * (t + 1):(p * n + i + 1) * (t + 1)] for i in range(n)]
+            for p in range(n)]
+    values = [[valh[(p * n + s) * n:(p * n + s + 1) * n] for s in range(n)] for p in range(n)]
+    part_ok, ack_ok = [], []
+    for i in range(n):
+        ok, row_tables = _check_parts(t, i + 1, [(None, rows[p][i]) for p in range(n)], ctab, dev)
+        part_ok.append(ok)
+        acks = [(p, s, values[p][s][i]) for p in range(n) for s in ack_senders[p]]
+        okh = _ack_checks(t, row_tables, acks, dev).cpu().tolist() if acks else []
+        ack_ok.append([None if v == CHECK_INVALID else v == CHECK_OK for v in okh])
+    complete = [p for p in range(n) if len(set(ack_senders[p])) > 2 * t]
+    ktab, o96, o48, st = _generate(t, ctab, n, complete, dev)
+    (stab, s96, s48, sst), pk = _key_shares(ktab, t + 1, n, dev)
+    sks = _secret_key_shares(
+        t, [[[(s, values[p][s][i]) for s in ack_senders[p]] for p in complete] for i in range(n)],
+        dev)
+    return {"commitments": commitments, "rows": rows, "values": values, "part_ok": part_ok,
+            "ack_ok": ack_ok, "complete": complete, "key_set": _encodings(o96, o48, st),
+            "key_shares": (stab, s96, s48, sst, pk), "secret_key_shares": sks}

@@ -42,8 +42,18 @@ compressed ones (48 / 96 bytes): `g1_prepare_compressed` and
 `g2_points_prepare_compressed` build the same tables from those,
 `g1_decompress` / `g2_decompress` turn them into the uncompressed form, and
 `decrypt_shares_grouped_wire` / `threshold_sign_grouped_wire` are the grouped
-functions with every received point in wire form.  There is no CPU fallback:
-without the library or a GPU the calls raise `HbrbcUnavailable`.
+functions with every received point in wire form.
+
+The sending side is here too, for a simulator or test network that hosts all
+N nodes: `create_decryption_shares` (`decrypt_share_no_verify`, line 161:
+[sk_i] U) and `create_signature_shares` (`sign_g2`, threshold_sign.rs:167:
+[sk_i] H) make the N C shares of C ciphertexts or documents in one launch of
+`g1_mul_prepared` / `g2_mul_prepared`, straight into the tables the checks and
+the combines read; the secret key shares come from hbbft_amd/keygen.py.  These
+multiplications branch on scalar bits and are not constant-time.
+
+There is no CPU fallback: without the library or a GPU the calls raise
+`HbrbcUnavailable`.
 """
 import ctypes
 
@@ -839,6 +849,118 @@ def _threshold_sign(documents, shares, threshold, public_key, device, wire):
             if res is not None:
                 outs[d] = res + (verh[j] == CHECK_OK,)
     return flags, outs
+
+
+# ---- share creation: what a node sends ----
+def _mul_prepared(g2, tab, table_count, rows, scalars, sidx, encode, stream):
+    """The body of g1_mul_prepared and g2_mul_prepared."""
+    torch = _torch()
+    L = lib()
+    entry, table_size, width = ((L.hbrbc_g2_mul_prepared, L.hbrbc_g2_points_size, G2_BYTES) if g2
+                                else (L.hbrbc_g1_mul_prepared, L.hbrbc_g1_prepared_size, G1_BYTES))
+    assert tab.numel() == table_size(table_count)
+    assert rows.dtype == torch.int32 and rows.dim() == 1 and rows.is_contiguous()
+    count = rows.shape[0]
+    assert scalars.dtype == torch.uint8 and scalars.dim() == 2 and scalars.shape[1] == FR_BYTES
+    assert scalars.is_contiguous() and tab.device == rows.device == scalars.device
+    nscalars = scalars.shape[0]
+    if sidx is None:
+        assert nscalars >= count, (nscalars, count)
+    else:
+        assert sidx.dtype == torch.int32 and sidx.shape == (count,) and sidx.is_contiguous()
+        assert sidx.device == rows.device
+    _need_gpu()
+    dev = rows.device
+    out = torch.empty(max(1, table_size(count)), dtype=torch.uint8, device=dev)
+    ou = oc = None
+    if encode:
+        ou = torch.empty((count, width), dtype=torch.uint8, device=dev)
+        oc = torch.empty((count, width // 2), dtype=torch.uint8, device=dev)
+    st = torch.empty((count,), dtype=torch.uint8, device=dev)
+    _check(entry(tab.data_ptr(), table_count, rows.data_ptr(), scalars.data_ptr(), nscalars,
+                 sidx.data_ptr() if sidx is not None else None, count, out.data_ptr(),
+                 ou.data_ptr() if encode else None, oc.data_ptr() if encode else None,
+                 st.data_ptr(), _stream(dev, stream)))
+    return out, ou, oc, st
+
+
+def g1_mul_prepared(a_prep, prepared_count, rows, scalars, sidx=None, encode=True, stream=None):
+    """Result j is [scalars[sidx[j]]] T[rows[j]] over T = a_prep, a g1_prepare
+    table of exactly `prepared_count` points: rows int32 [count], scalars uint8
+    [nscalars, 32] (big-endian, < r), sidx int32 [count] or None (scalar j;
+    nscalars >= count).  Returns (table uint8 -- the results as a g1_prepare
+    table of `count` points --, out96 uint8 [count, 96], out48 uint8 [count,
+    48] (both None without `encode`), status uint8 [count]: 0 ok, 1 infinity, 2
+    invalid table entry, row, sidx or scalar).  Not constant-time."""
+    return _mul_prepared(False, a_prep, prepared_count, rows, scalars, sidx, encode, stream)
+
+
+def g2_mul_prepared(tab, table_count, rows, scalars, sidx=None, encode=True, stream=None):
+    """g1_mul_prepared in G2: T = tab is a g2_points_prepare table of exactly
+    `table_count` points, the results a g2_points_prepare table of `count`
+    points with out192 uint8 [count, 192] and out96 uint8 [count, 96]."""
+    return _mul_prepared(True, tab, table_count, rows, scalars, sidx, encode, stream)
+
+
+def share_row(node, item, items):
+    """Row of (node i, item c) in the tables of create_decryption_shares and
+    create_signature_shares over `items` ciphertexts / documents: i * items +
+    c, node-major -- the lanes of a wave share one secret key share."""
+    return node * items + item
+
+
+def _create_shares(g2, secret_shares, points, device):
+    import numpy as np
+    torch = _torch()
+    for s in secret_shares:
+        if len(s) != FR_BYTES:
+            raise ValueError("secret key share of %d bytes, expected %d" % (len(s), FR_BYTES))
+    width = G2_BYTES if g2 else G1_COMPRESSED_BYTES
+    for p in points:
+        if len(p) != width:
+            raise ValueError("point of %d bytes, expected %d" % (len(p), width))
+    if not secret_shares or not points:
+        raise ValueError("no shares to create")
+    _need_gpu()
+    dev = "cuda:%d" % device
+    n, c = len(secret_shares), len(points)
+    if g2:
+        tab = g2_points_prepare(_g2_rows(points, dev))
+    else:
+        tab = g1_prepare_compressed(_g1_rows(points, dev, G1_COMPRESSED_BYTES))
+    sk = np.frombuffer(b"".join(bytes(s) for s in secret_shares), np.uint8).reshape(n, FR_BYTES)
+    lanes = torch.arange(n * c, dtype=torch.int32, device=dev)
+    rows = (lanes % max(c, 1)).contiguous()
+    sidx = torch.div(lanes, max(c, 1), rounding_mode="floor").to(torch.int32).contiguous()
+    out, ou, oc, st = _mul_prepared(g2, tab, c, rows, torch.from_numpy(sk.copy()).to(dev), sidx,
+                                    True, None)
+    return out, n * c, ou, oc, st
+
+
+def create_decryption_shares(secret_shares, us48, device=0):
+    """`decrypt_share_no_verify` (threshold_decrypt.rs:161) of every node for
+    every ciphertext: secret_shares = the N sk_i (32 bytes each), us48 = the U
+    of C ciphertexts (compressed G1, 48 bytes, decoded and checked once).  All
+    N C shares [sk_i] U_c come from one launch.  Returns (table, count, out96
+    uint8 [N C, 96], out48 uint8 [N C, 48] -- the wire form of a
+    DecryptionShare --, status uint8 [N C]): `table` is the g1_prepare table of
+    the count = N C shares, the share of (node i, ciphertext c) at row
+    share_row(i, c, C) = i C + c, which pairing_check_prepared_pts (a_prep,
+    with idx_c = the row's node) and decrypt_combine_prepared read as it is.
+    Status 1: a U at infinity or sk_i = 0; 2: a U that does not decode or
+    sk_i >= r.  Not constant-time: for simulations and test networks."""
+    return _create_shares(False, secret_shares, us48, device)
+
+
+def create_signature_shares(secret_shares, hashes192, device=0):
+    """`sign_g2` (threshold_sign.rs:167) of every node for every document:
+    hashes192 = H = hash_g2(doc) of C documents (uncompressed G2, 192 bytes;
+    the caller's, decoded and checked once).  Returns (table, count, out192
+    uint8 [N C, 192], out96 uint8 [N C, 96] -- the wire form of a
+    SignatureShare --, status) as create_decryption_shares: `table` is the
+    g2_points_prepare table that sig_check_prepared and sig_combine_prepared
+    read, (node i, document c) at row share_row(i, c, C)."""
+    return _create_shares(True, secret_shares, hashes192, device)
 
 
 def pairing_check(a, b, c, d):

@@ -684,6 +684,77 @@ int hbrbc_g1_decompress(const uint8_t *g1c, size_t count, uint8_t *out96, uint8_
 int hbrbc_g2_decompress(const uint8_t *g2c, size_t count, uint8_t *out192, uint8_t *status,
                         void *stream);
 
+/* ---- share creation: what a node sends -----------------------------------
+ * The entries above handle what a node receives; these make what it sends,
+ * for a simulator or test network that hosts every node:
+ *   `decrypt_share_no_verify`  [sk_i] U          (threshold_decrypt.rs:161)
+ *   `sign_g2`                  [sk_i] H          (threshold_sign.rs:167)
+ *   `Poly::commitment`, `BivarPoly::commitment`, `public_key_share`, the U of
+ *   `PublicKey::encrypt`       [s] G1::one()
+ *   `BivarPoly::row`, `Poly::evaluate`, and `generate`'s secret key share
+ *   (sync_key_gen.rs:413-417, :459, :523-524), in the scalar field Fr.
+ * Scalars are 32 big-endian bytes, canonical (< r).  Device memory, async on
+ * `stream`; no entry reads anything back.  The multiplications branch on the
+ * bits of the scalar: they are NOT constant-time and are meant for simulation
+ * and test networks, not for a node whose secret key an observer could time.
+ * hash_g1_g2, hash_g2, xor_with_hash, `pk.encrypt` / `sec_key.decrypt` of rows
+ * and values, and `BivarPoly::random` stay with the caller.
+ *
+ * [s_i] G1::one() for i < count: result i goes to `out_table`
+ * (hbrbc_g1_prepared_size(count) bytes) as entry i of a hbrbc_g1_prepare table
+ * over `count` points, bit for bit, and, where the pointers are non-null, to
+ * out96 + 96 i and out48 + 48 i in the encodings of the combine.
+ * status_out[i]: 0 ok, 1 the point at infinity (s = 0), 2 s >= r (zero
+ * bytes). */
+int hbrbc_g1_base_mul(const uint8_t *scalars, size_t count, void *out_table, uint8_t *out96,
+                      uint8_t *out48, uint8_t *status_out, void *stream);
+/* Result j < count is [scalars[sidx[j]]] T[rows[j]]: T a table of
+ * hbrbc_g1_prepare (hbrbc_g2_points_prepare) with exactly `prepared_count`
+ * (`table_count`) points, `scalars` holds nscalars scalars, rows and sidx are
+ * int32 per result.  A null sidx means sidx[j] = j, and nscalars must then be
+ * >= count.  Lanes that share a scalar should be adjacent (sort the results by
+ * sidx): a wave whose 64 lanes hold one scalar takes every branch as one.
+ * Results go to `out_table` (hbrbc_g1_prepared_size(count) /
+ * hbrbc_g2_points_size(count) bytes) in the form of hbrbc_g1_prepare /
+ * hbrbc_g2_points_prepare over `count` points, bit for bit -- every entry
+ * that reads such a table reads this one, and no second order-r check is due:
+ * a multiple of a checked point is in the subgroup -- and, where the pointers
+ * are non-null, to the uncompressed and compressed encodings (G1: out96 +
+ * 96 j, out48 + 48 j; G2: out192 + 192 j, out96 + 96 j).  status_out[j]: 0
+ * ok, 1 the point at infinity (a zero scalar or a table entry at infinity), 2
+ * an invalid table entry, a row outside the table, sidx[j] outside [0,
+ * nscalars) or a scalar >= r (zero bytes); an index out of range is a status,
+ * never a read out of range. */
+int hbrbc_g1_mul_prepared(const void *a_prepared, size_t prepared_count, const int32_t *rows,
+                          const uint8_t *scalars, size_t nscalars, const int32_t *sidx,
+                          size_t count, void *out_table, uint8_t *out96, uint8_t *out48,
+                          uint8_t *status_out, void *stream);
+int hbrbc_g2_mul_prepared(const void *table, size_t table_count, const int32_t *rows,
+                          const uint8_t *scalars, size_t nscalars, const int32_t *sidx,
+                          size_t count, void *out_table, uint8_t *out192, uint8_t *out96,
+                          uint8_t *status_out, void *stream);
+/* The Fr twin of hbrbc_g1_poly_eval_prepared, with the same ragged
+ * description: polynomial p has the coefficients scalars[rows[offsets[p] ..
+ * offsets[p + 1])], constant term first (offsets: polys + 1 entries, every
+ * range clamped to the last one, which the kernel reads itself).  Evaluation
+ * e is polynomial poly[e] at the raw x[e] (x = 0 gives the constant term, an
+ * empty polynomial 0): out + 32 e.  status_out[e]: 0 ok, 2 a coefficient >= r,
+ * a row outside [0, nscalars) or poly[e] outside [0, polys) (zero bytes).
+ * `BivarPoly::row(x)`: coefficient j is the polynomial over the entries (0..t,
+ * j) of the bivariate polynomial; `Poly::evaluate` directly. */
+int hbrbc_fr_poly_eval(const uint8_t *scalars, size_t nscalars, const int32_t *rows,
+                       const uint32_t *offsets, size_t polys, const int32_t *poly,
+                       const uint32_t *x, size_t evals, uint8_t *out, uint8_t *status_out,
+                       void *stream);
+/* Per group g the sum of a_j b_j mod r over j in [offsets[g], offsets[g + 1])
+ * (offsets: groups + 1 entries, every range clamped to `total`, the number of
+ * scalars in a and in b): out + 32 g.  status_out[g]: 0 ok (an empty group is
+ * 0), 2 an operand >= r (zero bytes).  With a = the coefficients of
+ * hbrbc_lagrange_coeffs and b = the values a node received, this is the
+ * `Poly::interpolate(..).evaluate(0)` of `generate`. */
+int hbrbc_fr_dot(const uint8_t *a, const uint8_t *b, const uint32_t *offsets, size_t groups,
+                 size_t total, uint8_t *out, uint8_t *status_out, void *stream);
+
 /* ---- the Broadcast state machine, batched --------------- */
 /* Many instances x nodes of `Broadcast` (broadcast.rs:228-558) in synchronous
  * rounds: what a node emits in round t is delivered in round t + 1, each node
