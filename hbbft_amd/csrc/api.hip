@@ -2837,4 +2837,27 @@ int hbrbc_sm_round(hbrbc_ctx *c, const hbrbc_sm_args *a, void *stream) {
     return HBRBC_OK;
 }
 
+// ---- the BinaryAgreement state machine, batched (ba_sim.hip) --------------
+size_t hbrbc_ba_state_bytes(size_t n, size_t queue_epochs) {
+    return ba_state_bytes(n, queue_epochs);
+}
+
+int hbrbc_ba_round(const hbrbc_ba_args *a, void *stream) {
+    if (!a) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (a->count == 0) return HBRBC_OK;
+    if (a->n == 0 || a->n > 255)
+        return fail(HBRBC_E_INVALID_ARG, "the state machine handles 1..255 validators");
+    if (a->max_out == 0 || a->queue_epochs == 0 || a->queue_epochs > 16 || a->coins == 0)
+        return fail(HBRBC_E_INVALID_ARG, "bad max_out / queue_epochs / coins");
+    if (a->form > HBRBC_BA_FORM_STAGED_W3) return fail(HBRBC_E_INVALID_ARG, "unknown launch form");
+    if (a->round < 0) return fail(HBRBC_E_INVALID_ARG, "negative round");
+    if (!a->input || !a->role || !a->flip || !a->ahead || !a->share_ok || !a->coin || !a->out ||
+        !a->out_count || !a->state || !a->decision || !a->decision_epoch || !a->fault_count ||
+        !a->emitted || (a->max_faults && !a->faults) || (a->round > 0 && (!a->in || !a->in_count)))
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_ba_round(*a, static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
 }  // extern "C"

@@ -370,4 +370,15 @@ __host__ __device__ inline size_t sm_state_bytes(size_t n, size_t roots) {
 }
 hipError_t launch_sm_round(const hbrbc_sm_args &a, int n, int f, int k, hipStream_t s);
 
+// BinaryAgreement state machine rounds (ba_sim.hip).  Per node: the core --
+// epoch u32, flags u32 and nine sender masks u32[9][W] (received_bval[2],
+// received_aux[2], Conf has false / has true, received_term[2], coin shares)
+// -- and the future-epoch ring u16[n][queue_epochs], rounded to 16 bytes.  An
+// instance's block holds the cores of its n nodes, then their rings.
+__host__ __device__ inline size_t ba_core_words(size_t n) { return 2 + 9 * ((n + 31) / 32); }
+__host__ __device__ inline size_t ba_state_bytes(size_t n, size_t queue_epochs) {
+    return (4 * ba_core_words(n) + 2 * n * queue_epochs + 15) & ~(size_t)15;
+}
+hipError_t launch_ba_round(const hbrbc_ba_args &a, hipStream_t s);
+
 }  // namespace hbrbc

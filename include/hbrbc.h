@@ -821,6 +821,84 @@ size_t hbrbc_sm_state_bytes(size_t n, size_t roots);
 /* One round for the hosted nodes of every instance (ctx gives n, f, k). */
 int hbrbc_sm_round(hbrbc_ctx *ctx, const hbrbc_sm_args *args, void *stream);
 
+/* ---- the BinaryAgreement state machine, batched ------------------------ */
+/* Many instances x nodes of `BinaryAgreement` (binary_agreement.rs:206-521,
+ * sbv_broadcast.rs:67-187, threshold_sign.rs:127-270) in the synchronous
+ * rounds of hbrbc_sm_round: what a node emits in round t is delivered in
+ * round t + 1, each node handling its inbox in (sender index, emission
+ * order); round 0 is propose(input) of every node that has an input.  All n
+ * nodes of an instance are hosted (one rank).  A message is a record of
+ * 1 + W uint32 words (W = ceil(n / 32)): word 0 = kind | value << 8 |
+ * tampered << 12 | epoch << 16 (kind: 0 BVal, 1 Aux, 2 Conf, 3 Term, 4 Coin;
+ * value: a bool, or the two bits of a Conf's BoolSet, 1 = {false}, 2 =
+ * {true}, 3 = both), words 1..W = recipient bits.  The coin travels by
+ * reference: a Coin record names its sender's signature share of coin slot
+ * q = (epoch - 2) / 3 (or a tampered copy); share_ok holds the outcome of the
+ * share check of each, coin the parity of the slot's combined signature (a
+ * BLS threshold signature is unique, so the parity does not depend on which
+ * f + 1 valid shares a node combined).  Records of the previous round sit in
+ * `in` ([count][n][max_out][1 + W], counts in in_count), this round's go to
+ * `out`; out_count bit 31 flags an overflow.  Messages of a future epoch wait
+ * in a ring of queue_epochs slots per sender; one beyond the ring sets
+ * emitted[1] bit 1 (the run is to be rejected).  Fault records: blamed node
+ * << 8 | FaultKind (binary_agreement/mod.rs:110-129 order, 5 = CoinFault(
+ * UnverifiedSignatureShareSender)). */
+#define HBRBC_BA_NONE 0xFF
+enum hbrbc_ba_role {            /* per instance and node: what LEAVES the node */
+    HBRBC_BA_HONEST = 0,
+    HBRBC_BA_SILENT = 1,        /* nothing */
+    HBRBC_BA_TWO_FACED = 2,     /* every record twice: as it is to the recipients outside the
+                                   instance's flip mask, complemented (b -> !b, {false} <->
+                                   {true}; both and Coin unchanged) to those inside */
+    HBRBC_BA_BAD_COIN = 3,      /* its Coin records carry the tampered flag */
+    HBRBC_BA_REPLAY = 4,        /* every record twice in a row */
+    HBRBC_BA_AHEAD = 5,         /* every record's epoch raised by the instance's `ahead` */
+    HBRBC_BA_REPLAY_AHEAD = 6   /* both: twice in a row, epoch raised (duplicates in the queue) */
+};
+enum hbrbc_ba_form {            /* hbrbc_ba_args.form */
+    HBRBC_BA_FORM_AUTO = 0,     /* by n: STAGED below 128, STAGED_W3 from there while an
+                                   instance's cores fit the LDS, GLOBAL beyond */
+    HBRBC_BA_FORM_GLOBAL = 1,   /* state read and written where it lies; 3 waves per SIMD */
+    HBRBC_BA_FORM_STAGED = 2,   /* epoch, flags and sender masks of a workgroup's instances in
+                                   LDS for the round (the queue ring stays in global memory) */
+    HBRBC_BA_FORM_STAGED_W3 = 3 /* the same at 3 waves per SIMD (fewer registers, more
+                                   resident waves) */
+};
+typedef struct hbrbc_ba_args {
+    size_t count;                 /* instances */
+    uint32_t n;                   /* validators per instance, 1..255; f = (n - 1) / 3 */
+    uint32_t max_out;             /* records per node per round */
+    uint32_t max_faults;          /* fault records kept per node */
+    uint32_t queue_epochs;        /* slots of the future-epoch ring per sender, 1..16 */
+    uint32_t coins;               /* coin slots in share_ok / coin */
+    int32_t round;
+    uint32_t form;                /* enum hbrbc_ba_form */
+    const uint8_t *input;         /* [count][n]: 0, 1 or NONE (no propose) */
+    const uint8_t *role;          /* [count][n] */
+    const uint32_t *flip;         /* [count][W]: the recipients a TWO_FACED node lies to */
+    const uint16_t *ahead;        /* [count]: epochs an AHEAD node adds */
+    const uint8_t *share_ok;      /* [count][coins][2][n]: share of node j (tampered copy) valid */
+    const uint8_t *coin;          /* [count][coins]: parity of the slot's signature */
+    const uint32_t *in;
+    const uint32_t *in_count;     /* [count][n] */
+    uint32_t *out;
+    uint32_t *out_count;          /* [count][n] */
+    uint8_t *state;               /* [count][n][hbrbc_ba_state_bytes], zeroed before round 0 */
+    uint8_t *decision;            /* [count][n]: 0 / 1, NONE before */
+    uint16_t *decision_epoch;     /* [count][n]: the epoch the node decided in */
+    uint16_t *faults;             /* [count][n][max_faults] */
+    uint32_t *fault_count;        /* [count][n] (may exceed max_faults) */
+    uint32_t *emitted;            /* [2]: [0] += records emitted this round, [1] |= 1 a node
+                                     emitted more than max_out, 2 a record for an epoch beyond
+                                     the queue ring, 4 a node reached a coin slot >= coins,
+                                     8 an epoch of 65535, 16 more than queue_epochs + 2
+                                     pending Term continuations (not reachable) */
+    const uint32_t *active;       /* NULL, or: the round returns at once when *active == 0 */
+} hbrbc_ba_args;
+size_t hbrbc_ba_state_bytes(size_t n, size_t queue_epochs);
+/* One round for every node of every instance. */
+int hbrbc_ba_round(const hbrbc_ba_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
