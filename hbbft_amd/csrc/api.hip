@@ -2860,4 +2860,23 @@ int hbrbc_ba_round(const hbrbc_ba_args *a, void *stream) {
     return HBRBC_OK;
 }
 
+// ---- Subset: phase 2 of a round, batched (subset_sim.hip) -----------------
+int hbrbc_subset_round(const hbrbc_subset_args *a, void *stream) {
+    if (!a) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (a->count == 0) return HBRBC_OK;
+    if (a->n == 0 || a->n > 255)
+        return fail(HBRBC_E_INVALID_ARG, "the state machine handles 1..255 validators");
+    if (a->max_out == 0 || a->queue_epochs == 0 || a->queue_epochs > 16 || a->coins == 0)
+        return fail(HBRBC_E_INVALID_ARG, "bad max_out / queue_epochs / coins");
+    if (a->round < 0) return fail(HBRBC_E_INVALID_ARG, "negative round");
+    if (!a->role || !a->flip || !a->ahead || !a->share_ok || !a->coin || !a->out ||
+        !a->out_count || !a->state || !a->decision || !a->decision_epoch || !a->fault_count ||
+        !a->output_root || !a->proposal || !a->node_state || !a->out_seq || !a->out_len ||
+        !a->emitted || (a->max_faults && !a->faults) || (a->round > 0 && (!a->in || !a->in_count)))
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_subset_round(*a, static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
 }  // extern "C"

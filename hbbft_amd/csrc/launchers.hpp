@@ -381,4 +381,8 @@ __host__ __device__ inline size_t ba_state_bytes(size_t n, size_t queue_epochs) 
 }
 hipError_t launch_ba_round(const hbrbc_ba_args &a, hipStream_t s);
 
+// Phase 2 of a Subset round (subset_sim.hip): the agreement tables are those
+// of launch_ba_round over count x n instances, always in the global form.
+hipError_t launch_subset_round(const hbrbc_subset_args &a, hipStream_t s);
+
 }  // namespace hbrbc

@@ -823,6 +823,9 @@ template <bool ONE, int LV, class Inbox>
 __device__ __forceinline__ void sm_node(const hbrbc_sm_args &a, int n, int f, int k, size_t g, size_t inst,
                         int local, uint8_t *st, const uint8_t *pok, const uint8_t *dok,
                         Inbox in) {
+    // LV: the handler set (Sm::deliver) in bits 0..1, HBRBC_SM_SUBSET in bit 2
+    constexpr int HS = LV & 3;
+    constexpr bool SUB = (LV & 4) != 0;
     const int me = (int)a.node_lo + local;
     const int W = (n + 31) / 32, C = (int)a.roots;
     const size_t sd = a.nodes;
@@ -853,12 +856,18 @@ __device__ __forceinline__ void sm_node(const hbrbc_sm_args &a, int n, int f, in
     m.faults = a.faults + g * (size_t)a.max_faults;
     m.nfault = a.fault_count[g];
     m.cache_in();
-    if (LV == 0 && a.round == 0) {
+    // SUB (the broadcasts of Subset proposal states, subset/proposal_state.rs:
+    // 91-113): a ProposalState that has its value, or was rejected, has dropped
+    // the Broadcast -- a node that enters the round with an output_root
+    // (HBRBC_SM_DROPPED included: a rejected proposal, a dead node) handles
+    // nothing, round 0 included
+    const bool off = SUB && a.output_root[inst * a.nodes + local] != kNone;
+    if (HS == 0 && a.round == 0) {
         // the proposer's broadcast() (broadcast.rs:123-137, 170-225): its input
         // step goes out unfiltered (VirtualNet::send_input; only deliveries to
         // faulty nodes pass the adversary)
         m.drop = false;
-        if (me == m.proposer && !(m.FLAGS() & FL_VALUE_SENT)) {
+        if (!off && me == m.proposer && !(m.FLAGS() & FL_VALUE_SENT)) {
             m.FLAGS() |= FL_VALUE_SENT;
             uint32_t *r = m.emit_rec(K_VALUE, kNone, 0, 0);
             if (r) {
@@ -883,10 +892,10 @@ __device__ __forceinline__ void sm_node(const hbrbc_sm_args &a, int n, int f, in
     } else {
         m.drop = m.role == R_SILENT;
         const bool is_faker = a.fake_from[inst] == (uint8_t)me;
-        const bool faker = LV == 0 && is_faker;
+        const bool faker = HS == 0 && is_faker;
         // (a smaller handler set has no injection: a fake_from node means the
         // caller's HBRBC_SM_NO_FAKE was wrong, reported like a stray record)
-        if (LV > 0 && is_faker) m.bad = true;
+        if (HS > 0 && is_faker) m.bad = true;
         // this node's bit in a record's recipient mask (the record pointer
         // keeps its address space: see HB_SM_CONSTAS)
         const int mw = me >> 5;
@@ -935,7 +944,11 @@ __device__ __forceinline__ void sm_node(const hbrbc_sm_args &a, int n, int f, in
                     }
                 }
                 if (!hit) continue;
-                m.template deliver<LV>(s, h0, k0);
+                // SUB: the Broadcast is dropped the moment it outputs -- a later
+                // record of the round (a late Value, a duplicate) neither emits
+                // nor logs
+                if (SUB && (off || (m.FLAGS() & FL_DECIDED))) continue;
+                m.template deliver<HS>(s, h0, k0);
                 if (faker && !(m.FLAGS() & FL_FAKE_DONE)) {
                     // after the first delivered message (tests/broadcast.rs:73-97)
                     m.FLAGS() |= FL_FAKE_DONE;
@@ -951,7 +964,7 @@ __device__ __forceinline__ void sm_node(const hbrbc_sm_args &a, int n, int f, in
     a.fault_count[g] = m.nfault;
     if (m.nout) atomicAdd(a.emitted, m.nout);
     if (m.overflow) atomicOr(a.emitted + 1, 1u);
-    if (LV > 0 && m.bad) atomicOr(a.emitted + 1, 2u);
+    if (HS > 0 && m.bad) atomicOr(a.emitted + 1, 2u);
 }
 
 __device__ __forceinline__ size_t sm_in_block(const hbrbc_sm_args &a, size_t inst, int s) {
@@ -1110,7 +1123,9 @@ static size_t sm_lds_bytes(const hbrbc_sm_args &a, int n, int ipb, bool grec = f
     return ((size_t)ipb * per + 15) & ~(size_t)15;
 }
 
-// One instantiation set per handler set (LV: see Sm::deliver).
+// One instantiation set per handler set (LV bits 0..1: see Sm::deliver) and
+// for HBRBC_SM_SUBSET (LV bit 2: see sm_node); the sets without the flag are
+// the code they were before it existed.
 template <int LV>
 static hipError_t launch_sm_form(const hbrbc_sm_args &a, int n, int f, int k, hipStream_t s) {
     const size_t threads = a.count * a.nodes;
@@ -1167,6 +1182,10 @@ hipError_t launch_sm_round(const hbrbc_sm_args &a, int n, int f, int k, hipStrea
     const char *le = getenv("HBRBC_SM_LEAN");
     const int lv = (a.flags & HBRBC_SM_NO_FAKE) && !(le && !strcmp(le, "0"))
                        ? (a.round >= 2 ? 2 : (a.round == 1 ? 1 : 0)) : 0;
+    if (a.flags & HBRBC_SM_SUBSET)
+        return lv == 2 ? launch_sm_form<6>(a, n, f, k, s)
+                       : (lv == 1 ? launch_sm_form<5>(a, n, f, k, s)
+                                  : launch_sm_form<4>(a, n, f, k, s));
     return lv == 2 ? launch_sm_form<2>(a, n, f, k, s)
                    : (lv == 1 ? launch_sm_form<1>(a, n, f, k, s) : launch_sm_form<0>(a, n, f, k, s));
 }

@@ -814,9 +814,20 @@ typedef struct hbrbc_sm_args {
                                      Echo, EchoHash, Ready and CanDecode records: round 1 runs a
                                      kernel without the Fake handler, rounds >= 2 one without the
                                      Value handler too (a record of a kind left out, or a
-                                     fake_from node, sets emitted[1] bit 1, the caller's error) */
+                                     fake_from node, sets emitted[1] bit 1, the caller's error).
+                                     HBRBC_SM_SUBSET: the instances are the broadcasts of Subset
+                                     proposal states (see hbrbc_subset_round): a node that
+                                     enters a round with output_root != NONE handles nothing
+                                     (round 0 included), and a node that decides takes no
+                                     further record of that round -- the ProposalState has
+                                     dropped the Broadcast */
 } hbrbc_sm_args;
 #define HBRBC_SM_NO_FAKE 1u
+#define HBRBC_SM_SUBSET 2u
+/* output_root of a broadcast its proposal state dropped without an output:
+ * written by hbrbc_subset_round for a rejected proposal, preset by the caller
+ * for a dead node (root slots are < 8) */
+#define HBRBC_SM_DROPPED 0xFE
 size_t hbrbc_sm_state_bytes(size_t n, size_t roots);
 /* One round for the hosted nodes of every instance (ctx gives n, f, k). */
 int hbrbc_sm_round(hbrbc_ctx *ctx, const hbrbc_sm_args *args, void *stream);
@@ -898,6 +909,78 @@ typedef struct hbrbc_ba_args {
 size_t hbrbc_ba_state_bytes(size_t n, size_t queue_epochs);
 /* One round for every node of every instance. */
 int hbrbc_ba_round(const hbrbc_ba_args *args, void *stream);
+
+/* ---- Subset, batched: N broadcasts and N agreements a node ------------- */
+/* Many instances x nodes of `Subset` (subset/subset.rs:103-169, subset/
+ * proposal_state.rs:30-173) in the synchronous rounds of the two state
+ * machines above.  Per Subset instance i there are n broadcast and n
+ * agreement instances, (i, p) at index i n + p.  A round is two launches:
+ * phase 1, hbrbc_sm_round with HBRBC_SM_SUBSET over the count n broadcast
+ * instances (proposer[i n + p] = p, all nodes hosted), handles every node's
+ * broadcast records; phase 2, hbrbc_subset_round, one thread per (instance,
+ * node), then
+ *  1. for every proposer in order whose broadcast has an output_root: an
+ *     Ongoing proposal becomes HasValue and calls propose(true) on its
+ *     agreement, an Accepted one becomes Complete(true) and is output;
+ *  2. handles the node's agreement records in (proposer, sender, emission)
+ *     order with the handlers of hbrbc_ba_round; a `true` decision accepts the
+ *     proposal (and outputs it if the value is there), a `false` one completes
+ *     it and writes HBRBC_SM_DROPPED into the broadcast's output_root; at the
+ *     record that takes the accepted count to N - f, propose(false) runs at
+ *     once on every proposal that still has its agreement, in proposer order
+ *     (those whose records of this round are still to come included); when
+ *     every proposal is complete the node outputs Done.
+ * Round 0 is Subset::propose of every live node: phase 1's round 0, then
+ * phase 2 with empty inboxes (it initialises the agreements' epoch-0 coin
+ * state and the proposal states: HBRBC_SM_DROPPED in output_root gives
+ * Complete(false), the caller's preset for a dead node).  The agreement
+ * tables keep the layouts of hbrbc_ba_args with count n instances.  The global
+ * state form only. */
+enum hbrbc_subset_proposal {    /* the proposal-state byte (proposal_state.rs:17-28) */
+    HBRBC_SUBSET_ONGOING = 0,
+    HBRBC_SUBSET_HAS_VALUE = 1,
+    HBRBC_SUBSET_ACCEPTED = 2,
+    HBRBC_SUBSET_COMPLETE_FALSE = 3,
+    HBRBC_SUBSET_COMPLETE_TRUE = 4
+};
+#define HBRBC_SUBSET_DONE 0xFF   /* the Done marker of an output sequence */
+typedef struct hbrbc_subset_args {
+    size_t count;                 /* Subset instances */
+    uint32_t n;                   /* validators per instance, 1..255; f = (n - 1) / 3 */
+    uint32_t max_out;             /* agreement records per node, proposer and round */
+    uint32_t max_faults;          /* agreement fault records kept per node and proposer */
+    uint32_t queue_epochs;        /* slots of the future-epoch ring per sender, 1..16 */
+    uint32_t coins;               /* coin slots in share_ok / coin */
+    int32_t round;
+    const uint8_t *role;          /* [count n][n]: enum hbrbc_ba_role */
+    const uint32_t *flip;         /* [count n][W] */
+    const uint16_t *ahead;        /* [count n] */
+    const uint8_t *share_ok;      /* [count n][coins][2][n] */
+    const uint8_t *coin;          /* [count n][coins] */
+    const uint32_t *in;
+    const uint32_t *in_count;     /* [count n][n] */
+    uint32_t *out;
+    uint32_t *out_count;          /* [count n][n]; every round clears the node's own counts */
+    uint8_t *state;               /* [count n][n][hbrbc_ba_state_bytes], zeroed before round 0 */
+    uint8_t *decision;            /* [count n][n]: 0 / 1, NONE before */
+    uint16_t *decision_epoch;     /* [count n][n] */
+    uint16_t *faults;             /* [count n][n][max_faults] */
+    uint32_t *fault_count;        /* [count n][n], zeroed before round 0 */
+    uint8_t *output_root;         /* [count n][n]: phase 1's; read, and HBRBC_SM_DROPPED written */
+    uint8_t *proposal;            /* [count n][n]: enum hbrbc_subset_proposal of node j about
+                                     proposer p at (i n + p) n + j; written in round 0 */
+    uint32_t *node_state;         /* [count][n]: accepted count | complete count << 8 | voted
+                                     false << 16 | Done << 17; written in round 0 */
+    uint8_t *out_seq;             /* [count][n][n + 1]: the accepted proposers in output order,
+                                     then HBRBC_SUBSET_DONE */
+    uint32_t *out_len;            /* [count][n], zeroed before round 0 */
+    uint32_t *emitted;            /* [2]: [0] += agreement records emitted this round, [1] |=
+                                     the flag bits of hbrbc_ba_args.emitted */
+    const uint32_t *active;       /* NULL, or: the round returns at once when *active == 0 (the
+                                     records of both protocols in the previous round) */
+} hbrbc_subset_args;
+/* Phase 2 of one round for every node of every instance. */
+int hbrbc_subset_round(const hbrbc_subset_args *args, void *stream);
 
 #ifdef __cplusplus
 }
