@@ -708,13 +708,13 @@ __global__ __launch_bounds__(kBlock) void leaf_hash_list_pl_kernel(
 
 // The same list balanced over the SIMDs.  A sponge is a serial chain, so a
 // list is as slow as its busiest SIMD: 86,016 sponges (validator cfg3 / cfg4)
-// are 84 per SIMD -- 1.3 one-lane waves, i.e. two waves of 4,395 VALU per
+// are 84 per SIMD -- 1.3 one-lane waves, i.e. two waves of 4,364 VALU per
 // permutation back to back on a quarter of the SIMDs, or 2.6 pair-lane waves
 // rounded up to three of ~2,950.  Here one 512-lane block per CU (8 waves, two
 // per SIMD) takes an equal share of the list: whole rounds of 256 sponges on
 // waves 0-3, one lane each, and a remainder of at most 128 on waves 4-7, two
 // lanes each (a larger remainder is one more one-lane round).  At 84 per SIMD
-// a SIMD then runs one wave of each form: 4,395 + 2,950 VALU per permutation.
+// a SIMD then runs one wave of each form: 4,364 + 2,950 VALU per permutation.
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void leaf_hash_list_mix_kernel(
     const uint8_t *__restrict__ shards, uint32_t S, RowMap rows, size_t inst_stride,
     const uint2 *__restrict__ list, const uint32_t *__restrict__ counter,
@@ -886,6 +886,18 @@ __global__ HB_SPONGE_ATTR void validate_kernel(
     const size_t ps = inst * dig_rows + (rows ? r : jj);   // proof slot
     const uint32_t nd = ndig[ps];
     const uint8_t *dig = digests + ps * dslots * 32;
+    // The walk is one permutation per level for every lane of the wave: the
+    // operand order is 16 selects, not a branch (a wave of consecutive proofs
+    // holds odd and even indices at every level, and two arms are two Keccak
+    // bodies, each run with half its lanes masked).  Sibling `used` sits at
+    // dig + used*32 whatever the hashes are, so the next one, and the root,
+    // are requested before the permutation that hides their latency.  Only
+    // slots below min(nd, dslots) are read, as the in-order walk reads them;
+    // past the last one the load repeats that slot and its value is unused.
+    const uint32_t last = min(nd, dslots) - 1u;   // used only where nd > 0
+    uint32_t s[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, rt[8];
+    if (nd && dslots) load_digest(dig, s);
+    load_digest(roots + inst * root_stride, rt);
     bool ok = true;
     while (lvl_n > 1) {
         if ((i ^ 1u) < lvl_n) {
@@ -893,13 +905,16 @@ __global__ HB_SPONGE_ATTR void validate_kernel(
                 ok = false;  // not enough levels in the proof
                 break;
             }
-            uint32_t s[8], t[8];
-            load_digest(dig + (size_t)used * 32, s);
             ++used;
-            if (i & 1u)
-                sha3_256_pair(s, d, t);
-            else
-                sha3_256_pair(d, s, t);
+            const bool odd = i & 1u;
+            uint32_t a[8], b[8], t[8];
+#pragma unroll
+            for (int w = 0; w < 8; ++w) {
+                a[w] = odd ? s[w] : d[w];
+                b[w] = odd ? d[w] : s[w];
+            }
+            load_digest(dig + (size_t)min(used, last) * 32, s);
+            sha3_256_pair(a, b, t);
 #pragma unroll
             for (int w = 0; w < 8; ++w) d[w] = t[w];
         }
@@ -907,8 +922,6 @@ __global__ HB_SPONGE_ATTR void validate_kernel(
         lvl_n = (lvl_n + 1) >> 1;
     }
     if (used != nd) ok = false;  // too many levels in the proof
-    uint32_t rt[8];
-    load_digest(roots + inst * root_stride, rt);
 #pragma unroll
     for (int w = 0; w < 8; ++w) ok = ok && (rt[w] == d[w]);
     ok_out[g] = ok ? 1 : 0;
@@ -963,10 +976,15 @@ __global__ __launch_bounds__(kBlock) void validate_pl_kernel(
             uint32_t sd[8], t[8];
             load_digest(dig + (size_t)used * 32, sd);
             ++used;
-            if (i & 1u)
-                sha3_256_pair_pl(sd, d, h, t);
-            else
-                sha3_256_pair_pl(d, sd, h, t);
+            // operand order by select, one permutation (validate_kernel)
+            const bool odd = i & 1u;
+            uint32_t a[8], b[8];
+#pragma unroll
+            for (int w = 0; w < 8; ++w) {
+                a[w] = odd ? sd[w] : d[w];
+                b[w] = odd ? d[w] : sd[w];
+            }
+            sha3_256_pair_pl(a, b, h, t);
 #pragma unroll
             for (int w = 0; w < 8; ++w) d[w] = t[w];
         }
