@@ -2879,4 +2879,22 @@ int hbrbc_subset_round(const hbrbc_subset_args *a, void *stream) {
     return HBRBC_OK;
 }
 
+// ---- HoneyBadger: phase 3 of a round, batched (hb_sim.hip) -----------------
+int hbrbc_hb_round(const hbrbc_hb_args *a, void *stream) {
+    if (!a) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (a->count == 0) return HBRBC_OK;
+    if (a->n == 0 || a->n > 255)
+        return fail(HBRBC_E_INVALID_ARG, "the state machine handles 1..255 validators");
+    if (a->roots == 0 || a->roots > 8) return fail(HBRBC_E_INVALID_ARG, "roots must be 1..8");
+    if (a->round < 0) return fail(HBRBC_E_INVALID_ARG, "negative round");
+    if (!a->inst_flags || !a->role || !a->ct_state || !a->undeserialisable || !a->share_ok ||
+        !a->output_root || !a->out_seq || !a->out_len || !a->out || !a->node_state ||
+        !a->done_round || !a->batch_round || !a->dstate || !a->mask || !a->fault_count ||
+        !a->emitted || (a->max_faults && !a->faults) || (a->round > 0 && !a->in))
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_hb_round(*a, static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
 }  // extern "C"

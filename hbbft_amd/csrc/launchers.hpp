@@ -385,4 +385,8 @@ hipError_t launch_ba_round(const hbrbc_ba_args &a, hipStream_t s);
 // of launch_ba_round over count x n instances, always in the global form.
 hipError_t launch_subset_round(const hbrbc_subset_args &a, hipStream_t s);
 
+// Phase 3 of a HoneyBadger round (hb_sim.hip): one thread per (instance, node,
+// proposer) over phase 2's output sequences and phase 1's output_root.
+hipError_t launch_hb_round(const hbrbc_hb_args &a, hipStream_t s);
+
 }  // namespace hbrbc

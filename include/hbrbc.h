@@ -982,6 +982,105 @@ typedef struct hbrbc_subset_args {
 /* Phase 2 of one round for every node of every instance. */
 int hbrbc_subset_round(const hbrbc_subset_args *args, void *stream);
 
+/* ---- HoneyBadger, batched: one epoch, Subset then N decryptions a node -- */
+/* One epoch of `HoneyBadger` (honey_badger/epoch_state.rs:195-395,
+ * threshold_decrypt.rs:115-253 as a message handler, honey_badger.rs:100-116,
+ * 172-185) for every node of `count` networks, in the rounds of the Subset
+ * above.  A round is three launches: hbrbc_sm_round, hbrbc_subset_round, then
+ * phase 3, hbrbc_hb_round, one thread per (instance, node, proposer).  A
+ * node's phase 3 does, in this order,
+ *  (a) the entries of phase 2's out_seq past the node's cursor, in sequence
+ *      order (with HBRBC_HB_ALL_AT_END none before Done is there): a
+ *      contribution of proposer p is Complete in a plain instance; in an
+ *      encrypted one ct_state of the delivered root slot gives the fault that
+ *      blames p or the ciphertext, then remove_invalid_shares logs its faults
+ *      in sender order, the node's own share is stored and emitted, try_output
+ *      runs.  Done fixes the accepted set and removes the decryption state of
+ *      every other proposer, one UnexpectedDecryptionShare per stored sender;
+ *  (b) the previous round's DecryptionShare records for p in (sender,
+ *      emission) order (not the node's own).
+ * The batch leaves at the first moment every accepted proposer is Complete
+ * after Done; HoneyBadger drops what arrives for the epoch after that: when
+ * the batch leaves in (a) no share record of the round is handled; when it
+ * leaves in (b), at p* -- the highest proposer whose decryption completes in
+ * this round -- the threads of proposers above p* handle none (a reduction
+ * over the node's proposer threads); from the next round on the node handles
+ * nothing.  BatchDeserializationFailed is logged with the batch.
+ * Ciphertexts, shares and plaintexts travel by reference: a share record is
+ * one byte per (instance, proposer, sender) and round,
+ *   bits 0..1 the number of copies (0..2), bit 2 + c the variant of copy c
+ *   (0 the sender's honest share, 1 its tampered one),
+ * and share_ok holds `verify_decryption_share` of both variants against the
+ * ciphertext of each root slot (g = sum lambda_i share_i does not depend on
+ * which f + 1 valid shares are combined, so the plaintext is the slot's).
+ * hash_g1_g2, xor_with_hash and the bincode of a Ciphertext stay with the
+ * caller, hence ct_state and undeserialisable are inputs.  Fault records:
+ * blamed node << 8 | kind (enum hbrbc_hb_fault). */
+enum hbrbc_hb_role {            /* per instance and node: the decryption layer's sending side */
+    HBRBC_HB_HONEST = 0,
+    HBRBC_HB_SILENT = 1,        /* sends no share */
+    HBRBC_HB_BAD_SHARE = 2,     /* sends its variant-1 share */
+    HBRBC_HB_TWICE = 3,         /* every share as two copies in one round */
+    HBRBC_HB_STRAY = 4,         /* in round 1, and again in the round after it sees Done, a
+                                   variant-1 share for every proposer, ahead of its own */
+    HBRBC_HB_ABSENT = 5         /* a dead node: handles and sends nothing */
+};
+enum hbrbc_hb_fault {
+    HBRBC_HB_UNEXPECTED_SHARE = 0,     /* UnexpectedDecryptionShare */
+    HBRBC_HB_DESERIALIZE_CT = 1,       /* DeserializeCiphertext */
+    HBRBC_HB_INVALID_CT = 2,           /* InvalidCiphertext */
+    HBRBC_HB_BATCH_DESERIALIZE = 3,    /* BatchDeserializationFailed */
+    HBRBC_HB_MULTIPLE_SHARES = 4,      /* DecryptionFault(MultipleDecryptionShares) */
+    HBRBC_HB_UNVERIFIED_SHARE = 5      /* DecryptionFault(UnverifiedDecryptionShareSender) */
+};
+enum hbrbc_hb_decryption {      /* dstate bits 0..2; bit 3 (HBRBC_HB_ACCEPTED): p was output */
+    HBRBC_HB_DS_ABSENT = 0,
+    HBRBC_HB_DS_NO_CIPHERTEXT = 1,     /* Ongoing, shares waiting for the ciphertext */
+    HBRBC_HB_DS_ONGOING = 2,           /* Ongoing with the ciphertext, own share sent */
+    HBRBC_HB_DS_COMPLETE = 3,
+    HBRBC_HB_DS_REMOVED = 4            /* removed at Done: the proposer was not accepted */
+};
+#define HBRBC_HB_ACCEPTED 8u
+#define HBRBC_HB_ENCRYPTED 1u    /* inst_flags: require_decryption */
+#define HBRBC_HB_ALL_AT_END 2u   /* inst_flags: SubsetHandlingStrategy::AllAtEnd */
+#define HBRBC_HB_NO_BATCH (-1)
+typedef struct hbrbc_hb_args {
+    size_t count;                 /* networks (Subset instances) */
+    uint32_t n;                   /* validators, 1..255; f = (n - 1) / 3; W = ceil(n / 32) */
+    uint32_t roots;               /* root slots per broadcast in the tables, 1..8 */
+    uint32_t max_faults;          /* fault records kept per node and proposer */
+    int32_t round;
+    const uint8_t *inst_flags;    /* [count]: HBRBC_HB_ENCRYPTED | HBRBC_HB_ALL_AT_END */
+    const uint8_t *role;          /* [count][n]: enum hbrbc_hb_role */
+    const uint8_t *ct_state;      /* [count n][roots]: 0 valid, 1 does not deserialise, 2 fails
+                                     Ciphertext::verify */
+    const uint8_t *undeserialisable; /* [count n][roots]: the contribution does not deserialise */
+    const uint8_t *share_ok;      /* [count n][roots][2][n] */
+    const uint8_t *output_root;   /* [count n][n]: phase 1's (the delivered root slot) */
+    const uint8_t *out_seq;       /* [count][n][n + 1]: phase 2's */
+    const uint32_t *out_len;      /* [count][n] */
+    const uint8_t *in;            /* [count n][n]: the previous round's share records, by
+                                     (proposer, sender) */
+    uint8_t *out;                 /* [count n][n]: this round's; zeroed by the caller */
+    uint32_t *node_state;         /* [count][n]: out_seq cursor | saw Done << 16 | batch out
+                                     << 17; zeroed before round 0 */
+    int32_t *done_round;          /* [count][n]: the round the node saw Done in */
+    int32_t *batch_round;         /* [count][n]: HBRBC_HB_NO_BATCH before round 0 */
+    uint8_t *dstate;              /* [count n][n]: enum hbrbc_hb_decryption | HBRBC_HB_ACCEPTED
+                                     of node j about proposer p at (i n + p) n + j; zeroed */
+    uint32_t *mask;               /* [count n][2 W][n]: words 0..W-1 the senders whose share is
+                                     stored, W..2W-1 the stored shares' variants; zeroed */
+    uint16_t *faults;             /* [count n][n][max_faults] */
+    uint32_t *fault_count;        /* [count n][n] (may exceed max_faults); zeroed */
+    uint32_t *emitted;            /* [2]: [0] += share records (copies) emitted this round,
+                                     [1] |= 1 a root slot, ct_state or role out of range, 2 an
+                                     out_seq entry or length out of range */
+    const uint32_t *active;       /* NULL, or: the round returns at once when *active == 0 (the
+                                     records of all three protocols in the previous round) */
+} hbrbc_hb_args;
+/* Phase 3 of one round for every node of every instance. */
+int hbrbc_hb_round(const hbrbc_hb_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
