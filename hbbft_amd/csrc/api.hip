@@ -699,6 +699,20 @@ bool spec_lds(size_t nin, size_t nout) {
     return nin >= 16 && nout >= 14;
 }
 
+// Chunk order of the specialised kernels: consecutive chunks on one XCD
+// (jit.hip gen_prologue; code objects `*_X*`).  Default where it measured
+// faster beyond the spread of alternating runs: the encoders of up to 32
+// inputs (frame+encode alone, cfg2 k = 6: 3.32-3.33 -> 3.16 ms, cfg3 k = 22:
+// 3.56-3.59 -> 3.46-3.49 ms, 7.42-7.46 -> 7.00-7.04 ms per step in the
+// pipeline) and of 64 and more (cfg5 k = 84: 8.69-8.75 -> 8.61-8.66 ms).  cfg4
+// (k = 44) is flat (2.80-2.81 vs 2.81-2.84 ms) and the pattern decoders are
+// flat or unmeasured: they keep the plain order.  HBRBC_JIT_XCD=0/1 overrides
+// for every program (A/B).
+bool spec_xcd(size_t nin, bool encoder) {
+    if (const char *e = getenv("HBRBC_JIT_XCD")) return !std::strcmp(e, "1");
+    return encoder && (nin <= 32 || nin >= 64);
+}
+
 // XOR-network form: 0 auto, 1 pairwise, 2 nibble-subset (HBRBC_JIT_NET, A/B).
 int spec_net() {
     if (const char *e = getenv("HBRBC_JIT_NET")) return std::max(0, std::min(2, atoi(e)));
@@ -723,13 +737,14 @@ int spec_wpe(size_t nin, size_t nout) {
 
 // Code-object name suffix of the variant options above (only where they
 // change the generated code: the LDS form needs 2..8 passes).
-std::string spec_suffix(size_t nin, size_t nout, int rt) {
+std::string spec_suffix(size_t nin, size_t nout, int rt, bool encoder) {
     const int npass = (int)((nout + rt - 1) / rt);
     std::string s;
     if (spec_lds(nin, nout) && npass >= 2 && npass <= 8) {
         s += "_L";
         if (spec_lds_stage()) s += std::to_string(spec_lds_stage());
     }
+    if (spec_xcd(nin, encoder)) s += "_X";
     if (spec_net()) s += "_n" + std::to_string(spec_net());
     if (spec_wpe(nin, nout)) s += "_w" + std::to_string(spec_wpe(nin, nout));
     return s;
@@ -739,9 +754,10 @@ void spec_variant(XorProgram &p) {
     const size_t nin = p.in_rows.size(), nout = p.out_rows.size();
     p.lds = spec_lds(nin, nout);
     p.lds_stage = spec_lds_stage();
+    p.xcd = spec_xcd(nin, p.fused);
     p.net = spec_net();
     p.wpe = spec_wpe(nin, nout);
-    p.name += spec_suffix(nin, nout, p.rt);
+    p.name += spec_suffix(nin, nout, p.rt, p.fused);
 }
 
 bool read_file(const std::string &path, std::vector<char> &out) {
@@ -2100,7 +2116,7 @@ int hbrbc_jit_encode_file_name(size_t data_shards, size_t parity_shards, size_t 
                                         groups[group].first, groups[group].second, rb,
                                         spec_sync(), spec_fdepth(), spec_spread(),
                                         spec_split()) +
-                     spec_suffix(data_shards, groups[group].second - groups[group].first, rt))
+                     spec_suffix(data_shards, groups[group].second - groups[group].first, rt, true))
             .substr(1);
     if (f.size() + 1 > buf_len) return fail(HBRBC_E_INVALID_ARG, "buffer too small");
     std::memcpy(buf, f.c_str(), f.size() + 1);

@@ -272,8 +272,18 @@ void gen_prologue(std::ostringstream &o, const XorProgram &p, bool fused, int np
          "    const int *__restrict__ pat, const unsigned long *__restrict__ slot_hash, int hash_slots,\n"
          "    int p_only, uint8_t *__restrict__ uf_payload, unsigned long uf_stride,\n"
          "    const int *__restrict__ uf_status) {\n"
-      << lds_decl
-      << "  const unsigned long inst = blockIdx.x / waves_per_row;\n";
+      << lds_decl;
+    // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2.
+    // p.xcd: workgroup b takes chunk (b % 8) * (grid / 8) + b / 8, so one XCD
+    // walks consecutive 2 KB chunks of a row: the lines two chunks share (row
+    // starts are 16-byte, not line aligned) and the payload lines their
+    // windows both read meet in one L2 instead of two
+    if (p.xcd)
+        o << "  unsigned bid_ = blockIdx.x;\n"
+             "  { const unsigned per_ = gridDim.x >> 3; if (bid_ < per_ * 8u) bid_ = (bid_ & 7u) * per_ + (bid_ >> 3); }\n";
+    else
+        o << "  const unsigned bid_ = blockIdx.x;\n";
+    o << "  const unsigned long inst = bid_ / waves_per_row;\n";
     if (p.guard) {
         // reconstruct of one cached erasure pattern: other patterns return
         char g[64];
@@ -287,7 +297,7 @@ void gen_prologue(std::ostringstream &o, const XorProgram &p, bool fused, int np
     // apart, so every load and store instruction of a wave covers 1 KB of
     // consecutive bytes instead of 64 pieces of 16 with 16-byte gaps
     o << "  const int wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);\n"
-         "  const unsigned wchunk = blockIdx.x - (unsigned)inst * waves_per_row, lane = threadIdx.x & 63u;\n"
+         "  const unsigned wchunk = bid_ - (unsigned)inst * waves_per_row, lane = threadIdx.x & 63u;\n"
       << (p.split ? "  unsigned off = wchunk * 2048u + lane * 16u;\n" : "  unsigned off = (wchunk * 64u + lane) * 32u;\n")
       << "  const bool active = off < row_bytes;\n"
          "  if (!active) off = row_bytes - 16u;\n"

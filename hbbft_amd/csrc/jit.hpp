@@ -45,6 +45,9 @@ struct XorProgram {
     // workgroup, planes shared through LDS; stages of lds_stage inputs
     bool lds = false;
     int lds_stage = 0;
+    // chunk order: a workgroup's chunk chosen so that each XCD walks
+    // consecutive chunks (jit.hip gen_prologue)
+    bool xcd = false;
     // network: 0 auto (nibble-subset for passes <= 8 rows, else pairwise),
     // 1 pairwise, 2 nibble-subset
     int net = 0;
