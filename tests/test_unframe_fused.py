@@ -3,8 +3,8 @@ the data rows; decode_check + a zero-fill fixup finish decode_from_shards,
 broadcast.rs:563-601) against the separate unframe kernel and the oracle:
 whole payload slots, lengths and statuses identical, for all-present, f and 2f
 erasures, too few shards, a tampered shard, a lying length prefix, and shard
-lengths that are not a multiple of 4 (byte-aligned payload stores in the
-generic kernel; with a specialised decoder such a call unframes separately)."""
+lengths that are not a multiple of 4 (byte-aligned 16-byte payload stores, in
+the generic kernel and in a specialised decoder's _uf programs alike)."""
 import os
 
 import numpy as np
@@ -105,8 +105,10 @@ def test_fused_unframe_in_specialised_decoder(torch_cuda, n, plen):
     """Instances of a pattern with a specialised (JIT) decoder write their
     payload from that decoder (first program: present data rows; every
     program: rebuilt data rows); instances of other patterns from the generic
-    kernel.  Whole slots equal the separate unframe's and the oracle's.  With S
-    % 4 != 0 the _uf programs do not apply and the call unframes separately."""
+    kernel.  Whole slots equal the separate unframe's and the oracle's.  The
+    _uf programs apply at any S (api.hip unframe_fusable; whole 16-byte chunks
+    at any byte alignment, the edge chunks by the fixup kernel): S % 4 is 0, 0,
+    2 and 3 here, and tests/test_xor_forms.py runs every residue."""
     torch = torch_cuda
     import hbbft_amd as hb
     f = (n - 1) // 3
