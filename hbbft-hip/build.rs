@@ -15,8 +15,9 @@ fn main() {
             let manifest = PathBuf::from(env::var("CARGO_MANIFEST_DIR").unwrap());
             let root = manifest.parent().expect("hbbft-hip sits beside hbbft_amd/").to_path_buf();
             let csrc = root.join("hbbft_amd").join("csrc");
-            for f in &["kernels.hip", "api.hip", "jit.hip", "wire.hip", "pairing.hip", "sim.hip",
-                       "version.cpp", "device_common.hpp", "launchers.hpp", "jit.hpp",
+            for f in &["kernels.hip", "api.hip", "api_pairing.hip", "jit.hip", "wire.hip",
+                       "pairing.hip", "sim.hip", "version.cpp", "device_common.hpp",
+                       "launchers.hpp", "api_internal.hpp", "pairing_tables.hpp", "jit.hpp",
                        "bls_consts.hpp", "Makefile"] {
                 println!("cargo:rerun-if-changed={}", csrc.join(f).display());
             }

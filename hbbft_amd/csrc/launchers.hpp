@@ -237,114 +237,6 @@ struct WireDecodeArgs {
 };
 hipError_t launch_wire_decode(const WireDecodeArgs &a, hipStream_t s);
 
-// BLS12-381 pairing checks (pairing.hip)
-hipError_t launch_pairing_miller(const uint8_t *g1, size_t g1_stride, const uint8_t *g2,
-                                 size_t g2_stride, size_t n, int pair_inputs, uint32_t *ws,
-                                 uint8_t *status, hipStream_t s);
-hipError_t launch_pairing_miller2(const uint8_t *g1, const uint8_t *g2, size_t count,
-                                  uint32_t *ws, uint8_t *status, hipStream_t s);
-size_t pairing_prepared_words(size_t points);
-hipError_t launch_g2_prepare(const uint8_t *g2, size_t count, uint32_t *prep, uint8_t *pst,
-                             hipStream_t s);
-hipError_t launch_pairing_miller_prepared(const uint8_t *g1, const uint32_t *prep,
-                                          const uint8_t *pst, const uint32_t *ib,
-                                          const uint32_t *id, size_t points, size_t count,
-                                          uint32_t *ws, uint8_t *status, hipStream_t s);
-size_t g1_key_words(size_t points);
-hipError_t launch_pairing_miller_prepared_pts(const uint32_t *atab, const uint8_t *ast,
-                                              const uint32_t *keys, const uint8_t *kst,
-                                              const uint32_t *ic, size_t nkeys,
-                                              const uint32_t *prep, const uint8_t *pst,
-                                              const uint32_t *ib, const uint32_t *id,
-                                              size_t points, size_t count, uint32_t *ws,
-                                              uint8_t *status, hipStream_t s);
-hipError_t launch_g1_prepare(const uint8_t *g1, size_t count, uint32_t *keys, uint8_t *kst,
-                             hipStream_t s);
-hipError_t launch_pairing_miller_prepared_keys(const uint8_t *g1_a, const uint32_t *keys,
-                                               const uint8_t *kst, const uint32_t *ic,
-                                               size_t nkeys, const uint32_t *prep,
-                                               const uint8_t *pst, const uint32_t *ib,
-                                               const uint32_t *id, size_t points, size_t count,
-                                               uint32_t *ws, uint8_t *status, hipStream_t s);
-hipError_t launch_pairing_final(const uint32_t *ws, size_t n_miller, size_t n_out, int per_out,
-                                const uint8_t *status, uint8_t *gt_out, uint8_t *ok_out,
-                                hipStream_t s);
-// decryption-share combine (pairing.hip): Lagrange coefficients, [k] P per
-// share from a g1_prepare table into a limb-major workspace of
-// g1_point_words(total) words, per-group sum and encodings
-size_t g1_point_words(size_t shares);
-hipError_t launch_lagrange(const uint32_t *idx, const uint32_t *offsets, size_t groups,
-                           size_t total, uint8_t *coeffs, uint8_t *status, hipStream_t s);
-hipError_t launch_g1_scalar_mul(const uint32_t *tab, const uint8_t *tst, size_t nprep,
-                                const int32_t *rows, const uint8_t *scalars, size_t total,
-                                uint32_t *ws, uint8_t *pst, hipStream_t s);
-hipError_t launch_g1_reduce_encode(const uint32_t *ws, const uint8_t *pst, const uint32_t *offsets,
-                                   size_t groups, size_t total, const uint8_t *lst, uint8_t *out96,
-                                   uint8_t *out48, uint8_t *status, hipStream_t s);
-// key generation (pairing.hip): ragged G1 polynomials over a g1_prepare table
-// evaluated at small integers (Horner), results in table form (otab, ost) and
-// optionally encoded; fixed-base checks [s] G1::one() == T[row]
-hipError_t launch_g1_horner(const uint32_t *tab, const uint8_t *tst, size_t nprep,
-                            const int32_t *rows, const uint32_t *offsets, size_t polys,
-                            const int32_t *poly, const uint32_t *x, size_t evals, uint32_t *otab,
-                            uint8_t *ost, uint8_t *out96, uint8_t *out48, uint8_t *status,
-                            hipStream_t s);
-hipError_t launch_g1_base_mul_check(const uint32_t *tab, const uint8_t *tst, size_t nprep,
-                                    const int32_t *rows, const uint8_t *scalars, size_t count,
-                                    uint8_t *ok, hipStream_t s);
-// threshold signatures (pairing.hip): decoded G2 points (a table of
-// g2_point_table_words(points) words), the share check e(K, P) == e(G1::one(),
-// S) with S from that table, [k] Q per share into a limb-major workspace of
-// g2_point_words(total) words, per-group sum, encodings and parity
-size_t g2_point_table_words(size_t points);
-size_t g2_point_words(size_t shares);
-hipError_t launch_g2_points(const uint8_t *g2, size_t count, uint32_t *tab, uint8_t *gst,
-                            hipStream_t s);
-hipError_t launch_pairing_miller_sig(const uint32_t *stab, const uint8_t *sst, size_t nsig,
-                                     const uint32_t *keys, const uint8_t *kst, const uint32_t *ic,
-                                     size_t nkeys, const uint32_t *prep, const uint8_t *pst,
-                                     const uint32_t *ih, size_t points, size_t count, uint32_t *ws,
-                                     uint8_t *status, hipStream_t s);
-hipError_t launch_g2_scalar_mul(const uint32_t *tab, const uint8_t *tst, size_t nprep,
-                                const int32_t *rows, const uint8_t *scalars, size_t total,
-                                uint32_t *ws, uint8_t *pst, hipStream_t s);
-hipError_t launch_g2_reduce_encode(const uint32_t *ws, const uint8_t *pst, const uint32_t *offsets,
-                                   size_t groups, size_t total, const uint8_t *lst,
-                                   uint8_t *out192, uint8_t *out96, uint8_t *parity,
-                                   uint8_t *status, hipStream_t s);
-// share creation (pairing.hip): [scalars[sidx[j]]] T[rows[j]] over a g1_prepare
-// / g2_points table and [s] G1::one(), results in table form (otab, ost) and
-// optionally encoded; ragged Fr polynomials evaluated at 32-bit integers and
-// ragged Fr dot products, 32 big-endian bytes per scalar
-hipError_t launch_g1_mul_table(const uint32_t *tab, const uint8_t *tst, size_t nprep,
-                               const int32_t *rows, const uint8_t *scalars, size_t nscalars,
-                               const int32_t *sidx, size_t count, uint32_t *otab, uint8_t *ost,
-                               uint8_t *out96, uint8_t *out48, uint8_t *status, hipStream_t s);
-hipError_t launch_g2_mul_table(const uint32_t *tab, const uint8_t *tst, size_t nprep,
-                               const int32_t *rows, const uint8_t *scalars, size_t nscalars,
-                               const int32_t *sidx, size_t count, uint32_t *otab, uint8_t *ost,
-                               uint8_t *out192, uint8_t *out96, uint8_t *status, hipStream_t s);
-hipError_t launch_g1_base_mul(const uint8_t *scalars, size_t count, uint32_t *otab, uint8_t *ost,
-                              uint8_t *out96, uint8_t *out48, uint8_t *status, hipStream_t s);
-hipError_t launch_fr_horner(const uint8_t *scalars, size_t nscalars, const int32_t *rows,
-                            const uint32_t *offsets, size_t polys, const int32_t *poly,
-                            const uint32_t *x, size_t evals, uint8_t *out, uint8_t *status,
-                            hipStream_t s);
-hipError_t launch_fr_dot(const uint8_t *a, const uint8_t *b, const uint32_t *offsets,
-                         size_t groups, size_t total, uint8_t *out, uint8_t *status,
-                         hipStream_t s);
-// compressed wire encodings (pairing.hip): the g1_prepare / g2_points tables
-// from 48- / 96-byte points, and compressed to uncompressed bytes with a
-// status byte per point (0 ok, 1 infinity, 2 invalid)
-hipError_t launch_g1_prepare_compressed(const uint8_t *g1c, size_t count, uint32_t *keys,
-                                        uint8_t *kst, hipStream_t s);
-hipError_t launch_g2_points_compressed(const uint8_t *g2c, size_t count, uint32_t *tab,
-                                       uint8_t *gst, hipStream_t s);
-hipError_t launch_g1_decompress(const uint8_t *g1c, size_t count, uint8_t *out96, uint8_t *status,
-                                hipStream_t s);
-hipError_t launch_g2_decompress(const uint8_t *g2c, size_t count, uint8_t *out192,
-                                uint8_t *status, hipStream_t s);
-
 hipError_t configure_kernels();
 
 // Broadcast state machine rounds (sim.hip).  Bytes per node: er u16[n]

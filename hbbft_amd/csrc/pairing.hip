@@ -34,7 +34,7 @@
 
 #include "bls_consts.hpp"
 #include "device_common.hpp"
-#include "launchers.hpp"
+#include "pairing_tables.hpp"
 
 namespace hbrbc {
 
@@ -2659,72 +2659,66 @@ __global__ __launch_bounds__(kPairBlock) __attribute__((amdgpu_waves_per_eu(kFin
 // The kernels run at 4 waves/SIMD (128 VGPRs, the rest of the tower state in
 // scratch); 1 and 2 waves measured within 5 %.
 hipError_t launch_pairing_miller(const uint8_t *g1, size_t g1_stride, const uint8_t *g2,
-                                 size_t g2_stride, size_t n, int pair_inputs, uint32_t *ws,
-                                 uint8_t *status, hipStream_t s) {
+                                 size_t g2_stride, size_t n, int pair_inputs, PairWs ws,
+                                 hipStream_t s) {
     if (n == 0) return hipSuccess;
     const unsigned blocks = (unsigned)((n + kPairBlock - 1) / kPairBlock);
     hipLaunchKernelGGL(miller_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g1, g1_stride, g2, g2_stride, n,
-                       pair_inputs, ws, status);
+                       pair_inputs, ws.gt, ws.status);
     return hipGetLastError();
 }
 
-hipError_t launch_pairing_miller2(const uint8_t *g1, const uint8_t *g2, size_t count,
-                                  uint32_t *ws, uint8_t *status, hipStream_t s) {
+hipError_t launch_pairing_miller2(const uint8_t *g1, const uint8_t *g2, size_t count, PairWs ws,
+                                  hipStream_t s) {
     if (count == 0) return hipSuccess;
     const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
-    hipLaunchKernelGGL(miller2_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g1, g2, count, ws,
-                       status);
+    hipLaunchKernelGGL(miller2_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g1, g2, count, ws.gt,
+                       ws.status);
     return hipGetLastError();
 }
 
 size_t pairing_prepared_words(size_t points) { return points * (size_t)kLines * kLineWords; }
 
-hipError_t launch_g2_prepare(const uint8_t *g2, size_t count, uint32_t *prep, uint8_t *pst,
-                             hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock) * 2;
-    hipLaunchKernelGGL(g2_prepare_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g2, count, prep,
-                       pst);
+hipError_t launch_g2_prepare(const uint8_t *g2, TableOut<G2Lines> prep, hipStream_t s) {
+    if (prep.count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((prep.count + kPairBlock - 1) / kPairBlock) * 2;
+    hipLaunchKernelGGL(g2_prepare_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g2, prep.count,
+                       prep.words, prep.status);
     return hipGetLastError();
 }
 
-hipError_t launch_pairing_miller_prepared(const uint8_t *g1, const uint32_t *prep,
-                                          const uint8_t *pst, const uint32_t *ib,
-                                          const uint32_t *id, size_t points, size_t count,
-                                          uint32_t *ws, uint8_t *status, hipStream_t s) {
+hipError_t launch_pairing_miller_prepared(const uint8_t *g1, Table<G2Lines> prep,
+                                          const uint32_t *ib, const uint32_t *id, size_t count,
+                                          PairWs ws, hipStream_t s) {
     if (count == 0) return hipSuccess;
-    if (points == 0) return hipErrorInvalidValue;
+    if (prep.count == 0) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
     hipLaunchKernelGGL(miller_prepared_kernel<false>, dim3(blocks), dim3(kPairBlock), 0, s, g1,
-                       nullptr, nullptr, nullptr, (size_t)0, prep, pst, ib, id, points, count, ws,
-                       status);
+                       nullptr, nullptr, nullptr, (size_t)0, prep.words, prep.status, ib, id,
+                       prep.count, count, ws.gt, ws.status);
     return hipGetLastError();
 }
 
 size_t g1_key_words(size_t points) { return points * (size_t)kG1KeyWords; }
 
-hipError_t launch_pairing_miller_prepared_pts(const uint32_t *atab, const uint8_t *ast,
-                                              const uint32_t *keys, const uint8_t *kst,
-                                              const uint32_t *ic, size_t nkeys,
-                                              const uint32_t *prep, const uint8_t *pst,
-                                              const uint32_t *ib, const uint32_t *id,
-                                              size_t points, size_t count, uint32_t *ws,
-                                              uint8_t *status, hipStream_t s) {
+hipError_t launch_pairing_miller_prepared_pts(Table<G1Keys> a, Table<G1Keys> keys,
+                                              const uint32_t *ic, Table<G2Lines> prep,
+                                              const uint32_t *ib, const uint32_t *id, size_t count,
+                                              PairWs ws, hipStream_t s) {
     if (count == 0) return hipSuccess;
-    if (points == 0 || nkeys == 0) return hipErrorInvalidValue;
+    if (prep.count == 0 || keys.count == 0) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
     hipLaunchKernelGGL((miller_prepared_kernel<true, true>), dim3(blocks), dim3(kPairBlock), 0, s,
-                       nullptr, keys, kst, ic, nkeys, prep, pst, ib, id, points, count, ws, status,
-                       atab, ast);
+                       nullptr, keys.words, keys.status, ic, keys.count, prep.words, prep.status,
+                       ib, id, prep.count, count, ws.gt, ws.status, a.words, a.status);
     return hipGetLastError();
 }
 
-hipError_t launch_g1_prepare(const uint8_t *g1, size_t count, uint32_t *keys, uint8_t *kst,
-                             hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
-    hipLaunchKernelGGL(g1_prepare_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g1, count, keys,
-                       kst);
+hipError_t launch_g1_prepare(const uint8_t *g1, TableOut<G1Keys> keys, hipStream_t s) {
+    if (keys.count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((keys.count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g1_prepare_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g1, keys.count,
+                       keys.words, keys.status);
     return hipGetLastError();
 }
 
@@ -2739,13 +2733,12 @@ hipError_t launch_lagrange(const uint32_t *idx, const uint32_t *offsets, size_t 
     return hipGetLastError();
 }
 
-hipError_t launch_g1_scalar_mul(const uint32_t *tab, const uint8_t *tst, size_t nprep,
-                                const int32_t *rows, const uint8_t *scalars, size_t total,
-                                uint32_t *ws, uint8_t *pst, hipStream_t s) {
+hipError_t launch_g1_scalar_mul(Table<G1Keys> tab, const int32_t *rows, const uint8_t *scalars,
+                                size_t total, uint32_t *ws, uint8_t *pst, hipStream_t s) {
     if (total == 0) return hipSuccess;
     const unsigned blocks = (unsigned)((total + kPairBlock - 1) / kPairBlock);
-    hipLaunchKernelGGL(g1_scalar_mul_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab, tst, nprep,
-                       rows, scalars, total, ws, pst);
+    hipLaunchKernelGGL(g1_scalar_mul_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab.words,
+                       tab.status, tab.count, rows, scalars, total, ws, pst);
     return hipGetLastError();
 }
 
@@ -2759,59 +2752,56 @@ hipError_t launch_g1_reduce_encode(const uint32_t *ws, const uint8_t *pst, const
     return hipGetLastError();
 }
 
-hipError_t launch_g1_horner(const uint32_t *tab, const uint8_t *tst, size_t nprep,
-                            const int32_t *rows, const uint32_t *offsets, size_t polys,
-                            const int32_t *poly, const uint32_t *x, size_t evals, uint32_t *otab,
-                            uint8_t *ost, uint8_t *out96, uint8_t *out48, uint8_t *status,
+hipError_t launch_g1_horner(Table<G1Keys> tab, const int32_t *rows, const uint32_t *offsets,
+                            size_t polys, const int32_t *poly, const uint32_t *x,
+                            TableOut<G1Keys> out, uint8_t *out96, uint8_t *out48, uint8_t *status,
                             hipStream_t s) {
-    if (evals == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((evals + kPairBlock - 1) / kPairBlock);
-    hipLaunchKernelGGL(g1_horner_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab, tst, nprep,
-                       rows, offsets, polys, poly, x, evals, otab, ost, out96, out48, status);
+    if (out.count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((out.count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g1_horner_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab.words,
+                       tab.status, tab.count, rows, offsets, polys, poly, x, out.count, out.words,
+                       out.status, out96, out48, status);
     return hipGetLastError();
 }
 
-hipError_t launch_g1_base_mul_check(const uint32_t *tab, const uint8_t *tst, size_t nprep,
-                                    const int32_t *rows, const uint8_t *scalars, size_t count,
-                                    uint8_t *ok, hipStream_t s) {
+hipError_t launch_g1_base_mul_check(Table<G1Keys> tab, const int32_t *rows, const uint8_t *scalars,
+                                    size_t count, uint8_t *ok, hipStream_t s) {
     if (count == 0) return hipSuccess;
     const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
-    hipLaunchKernelGGL(g1_base_mul_check_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab, tst,
-                       nprep, rows, scalars, count, ok);
+    hipLaunchKernelGGL(g1_base_mul_check_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab.words,
+                       tab.status, tab.count, rows, scalars, count, ok);
     return hipGetLastError();
 }
 
 size_t g2_point_table_words(size_t points) { return points * (size_t)kG2PtWords; }
 size_t g2_point_words(size_t shares) { return shares * (sizeof(PtProj<Fp2>) / 4); }
 
-hipError_t launch_g2_points(const uint8_t *g2, size_t count, uint32_t *tab, uint8_t *gst,
-                            hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
-    hipLaunchKernelGGL(g2_points_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g2, count, tab, gst);
+hipError_t launch_g2_points(const uint8_t *g2, TableOut<G2Points> tab, hipStream_t s) {
+    if (tab.count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((tab.count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g2_points_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g2, tab.count,
+                       tab.words, tab.status);
     return hipGetLastError();
 }
 
-hipError_t launch_pairing_miller_sig(const uint32_t *stab, const uint8_t *sst, size_t nsig,
-                                     const uint32_t *keys, const uint8_t *kst, const uint32_t *ic,
-                                     size_t nkeys, const uint32_t *prep, const uint8_t *pst,
-                                     const uint32_t *ih, size_t points, size_t count, uint32_t *ws,
-                                     uint8_t *status, hipStream_t s) {
+hipError_t launch_pairing_miller_sig(Table<G2Points> sig, Table<G1Keys> keys, const uint32_t *ic,
+                                     Table<G2Lines> prep, const uint32_t *ih, size_t count,
+                                     PairWs ws, hipStream_t s) {
     if (count == 0) return hipSuccess;
-    if (points == 0 || nkeys == 0) return hipErrorInvalidValue;
+    if (prep.count == 0 || keys.count == 0) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
-    hipLaunchKernelGGL(miller_sig_kernel, dim3(blocks), dim3(kPairBlock), 0, s, stab, sst, nsig,
-                       keys, kst, ic, nkeys, prep, pst, ih, points, count, ws, status);
+    hipLaunchKernelGGL(miller_sig_kernel, dim3(blocks), dim3(kPairBlock), 0, s, sig.words,
+                       sig.status, sig.count, keys.words, keys.status, ic, keys.count, prep.words,
+                       prep.status, ih, prep.count, count, ws.gt, ws.status);
     return hipGetLastError();
 }
 
-hipError_t launch_g2_scalar_mul(const uint32_t *tab, const uint8_t *tst, size_t nprep,
-                                const int32_t *rows, const uint8_t *scalars, size_t total,
-                                uint32_t *ws, uint8_t *pst, hipStream_t s) {
+hipError_t launch_g2_scalar_mul(Table<G2Points> tab, const int32_t *rows, const uint8_t *scalars,
+                                size_t total, uint32_t *ws, uint8_t *pst, hipStream_t s) {
     if (total == 0) return hipSuccess;
     const unsigned blocks = (unsigned)((total + kPairBlock - 1) / kPairBlock);
-    hipLaunchKernelGGL(g2_scalar_mul_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab, tst, nprep,
-                       rows, scalars, total, ws, pst);
+    hipLaunchKernelGGL(g2_scalar_mul_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab.words,
+                       tab.status, tab.count, rows, scalars, total, ws, pst);
     return hipGetLastError();
 }
 
@@ -2826,34 +2816,34 @@ hipError_t launch_g2_reduce_encode(const uint32_t *ws, const uint8_t *pst, const
     return hipGetLastError();
 }
 
-hipError_t launch_g1_mul_table(const uint32_t *tab, const uint8_t *tst, size_t nprep,
-                               const int32_t *rows, const uint8_t *scalars, size_t nscalars,
-                               const int32_t *sidx, size_t count, uint32_t *otab, uint8_t *ost,
+hipError_t launch_g1_mul_table(Table<G1Keys> tab, const int32_t *rows, const uint8_t *scalars,
+                               size_t nscalars, const int32_t *sidx, TableOut<G1Keys> out,
                                uint8_t *out96, uint8_t *out48, uint8_t *status, hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
-    hipLaunchKernelGGL(g1_mul_table_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab, tst, nprep,
-                       rows, scalars, nscalars, sidx, count, otab, ost, out96, out48, status);
+    if (out.count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((out.count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g1_mul_table_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab.words,
+                       tab.status, tab.count, rows, scalars, nscalars, sidx, out.count, out.words,
+                       out.status, out96, out48, status);
     return hipGetLastError();
 }
 
-hipError_t launch_g2_mul_table(const uint32_t *tab, const uint8_t *tst, size_t nprep,
-                               const int32_t *rows, const uint8_t *scalars, size_t nscalars,
-                               const int32_t *sidx, size_t count, uint32_t *otab, uint8_t *ost,
+hipError_t launch_g2_mul_table(Table<G2Points> tab, const int32_t *rows, const uint8_t *scalars,
+                               size_t nscalars, const int32_t *sidx, TableOut<G2Points> out,
                                uint8_t *out192, uint8_t *out96, uint8_t *status, hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
-    hipLaunchKernelGGL(g2_mul_table_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab, tst, nprep,
-                       rows, scalars, nscalars, sidx, count, otab, ost, out192, out96, status);
+    if (out.count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((out.count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g2_mul_table_kernel, dim3(blocks), dim3(kPairBlock), 0, s, tab.words,
+                       tab.status, tab.count, rows, scalars, nscalars, sidx, out.count, out.words,
+                       out.status, out192, out96, status);
     return hipGetLastError();
 }
 
-hipError_t launch_g1_base_mul(const uint8_t *scalars, size_t count, uint32_t *otab, uint8_t *ost,
-                              uint8_t *out96, uint8_t *out48, uint8_t *status, hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
-    hipLaunchKernelGGL(g1_base_mul_kernel, dim3(blocks), dim3(kPairBlock), 0, s, scalars, count,
-                       otab, ost, out96, out48, status);
+hipError_t launch_g1_base_mul(const uint8_t *scalars, TableOut<G1Keys> out, uint8_t *out96,
+                              uint8_t *out48, uint8_t *status, hipStream_t s) {
+    if (out.count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((out.count + kPairBlock - 1) / kPairBlock);
+    hipLaunchKernelGGL(g1_base_mul_kernel, dim3(blocks), dim3(kPairBlock), 0, s, scalars,
+                       out.count, out.words, out.status, out96, out48, status);
     return hipGetLastError();
 }
 
@@ -2878,21 +2868,19 @@ hipError_t launch_fr_dot(const uint8_t *a, const uint8_t *b, const uint32_t *off
     return hipGetLastError();
 }
 
-hipError_t launch_g1_prepare_compressed(const uint8_t *g1c, size_t count, uint32_t *keys,
-                                        uint8_t *kst, hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
+hipError_t launch_g1_prepare_compressed(const uint8_t *g1c, TableOut<G1Keys> keys, hipStream_t s) {
+    if (keys.count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((keys.count + kPairBlock - 1) / kPairBlock);
     hipLaunchKernelGGL(g1_prepare_compressed_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g1c,
-                       count, keys, kst);
+                       keys.count, keys.words, keys.status);
     return hipGetLastError();
 }
 
-hipError_t launch_g2_points_compressed(const uint8_t *g2c, size_t count, uint32_t *tab,
-                                       uint8_t *gst, hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
+hipError_t launch_g2_points_compressed(const uint8_t *g2c, TableOut<G2Points> tab, hipStream_t s) {
+    if (tab.count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((tab.count + kPairBlock - 1) / kPairBlock);
     hipLaunchKernelGGL(g2_points_compressed_kernel, dim3(blocks), dim3(kPairBlock), 0, s, g2c,
-                       count, tab, gst);
+                       tab.count, tab.words, tab.status);
     return hipGetLastError();
 }
 
@@ -2914,27 +2902,25 @@ hipError_t launch_g2_decompress(const uint8_t *g2c, size_t count, uint8_t *out19
     return hipGetLastError();
 }
 
-hipError_t launch_pairing_miller_prepared_keys(const uint8_t *g1_a, const uint32_t *keys,
-                                               const uint8_t *kst, const uint32_t *ic,
-                                               size_t nkeys, const uint32_t *prep,
-                                               const uint8_t *pst, const uint32_t *ib,
-                                               const uint32_t *id, size_t points, size_t count,
-                                               uint32_t *ws, uint8_t *status, hipStream_t s) {
+hipError_t launch_pairing_miller_prepared_keys(const uint8_t *g1_a, Table<G1Keys> keys,
+                                               const uint32_t *ic, Table<G2Lines> prep,
+                                               const uint32_t *ib, const uint32_t *id, size_t count,
+                                               PairWs ws, hipStream_t s) {
     if (count == 0) return hipSuccess;
-    if (points == 0 || nkeys == 0) return hipErrorInvalidValue;
+    if (prep.count == 0 || keys.count == 0) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)((count + kPairBlock - 1) / kPairBlock);
     hipLaunchKernelGGL(miller_prepared_kernel<true>, dim3(blocks), dim3(kPairBlock), 0, s, g1_a,
-                       keys, kst, ic, nkeys, prep, pst, ib, id, points, count, ws, status);
+                       keys.words, keys.status, ic, keys.count, prep.words, prep.status, ib, id,
+                       prep.count, count, ws.gt, ws.status);
     return hipGetLastError();
 }
 
-hipError_t launch_pairing_final(const uint32_t *ws, size_t n_miller, size_t n_out, int per_out,
-                                const uint8_t *status, uint8_t *gt_out, uint8_t *ok_out,
-                                hipStream_t s) {
+hipError_t launch_pairing_final(PairWs ws, size_t n_miller, size_t n_out, int per_out,
+                                uint8_t *gt_out, uint8_t *ok_out, hipStream_t s) {
     if (n_out == 0) return hipSuccess;
     const unsigned blocks = (unsigned)((n_out + kPairBlock - 1) / kPairBlock);
-    hipLaunchKernelGGL(final_exp_kernel, dim3(blocks), dim3(kPairBlock), 0, s, ws, n_miller, n_out, per_out,
-                       status, gt_out, ok_out);
+    hipLaunchKernelGGL(final_exp_kernel, dim3(blocks), dim3(kPairBlock), 0, s, ws.gt, n_miller, n_out, per_out,
+                       ws.status, gt_out, ok_out);
     return hipGetLastError();
 }
 

@@ -130,6 +130,13 @@ def pairing_check_batch(g1, g2, ws=None, stream=None):
     return ok
 
 
+def _table_sized(tab, size):
+    """A prepared table must hold exactly `size` bytes: the entries find its
+    status bytes at an offset that depends on the count it was prepared with.
+    (The preparations allocate one byte for a table of no points.)"""
+    return tab.numel() == size or (size == 0 and tab.numel() == 1)
+
+
 def g2_prepare(g2, stream=None):
     """Prepare G2 points (uint8 [n, 192]) once: the Miller-loop lines every
     check against them reuses (the crate's G2Prepared).  Returns the device
@@ -154,6 +161,7 @@ def pairing_check_prepared(g1, prep, points, idx_b, idx_d, ws=None, stream=None)
     assert idx_b.shape == (count,) and idx_d.shape == (count,)
     assert idx_b.dtype == torch.int32 and idx_d.dtype == torch.int32
     assert idx_b.is_contiguous() and idx_d.is_contiguous()
+    assert _table_sized(prep, lib().hbrbc_g2_prepared_size(points))
     # an index outside [0, points) makes that check's outcome 2 (invalid) on the device
     ok = torch.empty((count,), dtype=torch.uint8, device=g1.device)
     if ws is None:
@@ -230,6 +238,8 @@ def pairing_check_prepared_keys(shares, keys, key_points, idx_c, prep, points, i
     assert shares.shape == (count, G1_BYTES) and shares.is_contiguous()
     for t in (idx_b, idx_c, idx_d):
         assert t.shape == (count,) and t.dtype == torch.int32 and t.is_contiguous()
+    assert _table_sized(keys, lib().hbrbc_g1_prepared_size(key_points))
+    assert _table_sized(prep, lib().hbrbc_g2_prepared_size(points))
     ok = torch.empty((count,), dtype=torch.uint8, device=shares.device)
     if ws is None:
         ws = workspace(count, shares.device.index)
@@ -250,7 +260,9 @@ def pairing_check_prepared_pts(a_prep, count, keys, key_points, idx_c, prep, poi
     torch = _torch()
     for t in (idx_b, idx_c, idx_d):
         assert t.shape == (count,) and t.dtype == torch.int32 and t.is_contiguous()
-    assert a_prep.numel() >= lib().hbrbc_g1_prepared_size(count)
+    assert _table_sized(a_prep, lib().hbrbc_g1_prepared_size(count))
+    assert _table_sized(keys, lib().hbrbc_g1_prepared_size(key_points))
+    assert _table_sized(prep, lib().hbrbc_g2_prepared_size(points))
     ok = torch.empty((count,), dtype=torch.uint8, device=a_prep.device)
     if ws is None:
         ws = workspace(count, a_prep.device.index)

@@ -461,7 +461,16 @@ int hbrbc_pairing_check_batch(const uint8_t *g1, const uint8_t *g2, size_t count
  * each point, computed once and shared by every check against it (hbbft:
  * the N decryption shares of a ciphertext are all checked against its H and
  * W).  `prepared` >= hbrbc_g2_prepared_size(count) bytes of device memory;
- * an invalid point is marked there and fails every check that uses it. */
+ * an invalid point is marked there and fails every check that uses it.
+ *
+ * Table layout, for all three kinds of prepared table (hbrbc_g2_prepare,
+ * hbrbc_g1_prepare, hbrbc_g2_points_prepare and the entries that write their
+ * results in one of these forms): the coordinates of the `points` entries,
+ * padded to 256 bytes, then one status byte per entry.  The status bytes thus
+ * sit at an offset that depends on the count the table was prepared with:
+ * every entry that takes a table takes that count with it (`points`,
+ * `key_points`, `prepared_count`, `sig_count`, `table_count`), whatever rows
+ * the call uses. */
 size_t hbrbc_g2_prepared_size(size_t points);
 int hbrbc_g2_prepare(const uint8_t *g2, size_t count, void *prepared, void *stream);
 /* count checks e(a_i, P[idx_b[i]]) == e(c_i, P[idx_d[i]]) against prepared
@@ -479,7 +488,8 @@ int hbrbc_pairing_check_prepared(const uint8_t *g1, const void *prepared, size_t
  * checked once.  hbrbc_g1_prepare decodes and checks `count` G1 points once
  * (as any G1 input: canonical, on the curve, order r) into `prepared` >=
  * hbrbc_g1_prepared_size(count) bytes of device memory; an invalid point is
- * marked there and fails every check that uses it.  Device memory, async. */
+ * marked there and fails every check that uses it.  Device memory, async.
+ * Table layout: see hbrbc_g2_prepared_size. */
 size_t hbrbc_g1_prepared_size(size_t points);
 int hbrbc_g1_prepare(const uint8_t *g1, size_t count, void *prepared, void *stream);
 /* count checks e(a_i, P[idx_b[i]]) == e(K[idx_c[i]], P[idx_d[i]]) with K the
@@ -531,8 +541,7 @@ int hbrbc_lagrange_coeffs(const uint32_t *idx, const uint32_t *offsets, size_t g
                           uint8_t *coeffs_out, uint8_t *status_out, void *stream);
 /* Per group sum_j scalars[j] * T[rows[j]] over a table T of hbrbc_g1_prepare:
  * rows int32 per share, scalars 32 big-endian bytes per share.
- * `prepared_count` is the count the table was prepared with (the position of
- * its status bytes depends on it: pass that count, whatever the rows use).
+ * `prepared_count` is the table's count (see hbrbc_g2_prepared_size).
  * A zero scalar and a table entry at infinity contribute the identity. */
 int hbrbc_g1_lincomb_prepared(const void *a_prepared, size_t prepared_count, const int32_t *rows,
                               const uint8_t *scalars, const uint32_t *offsets, size_t groups,
@@ -608,7 +617,8 @@ int hbrbc_g1_base_mul_check(const void *a_prepared, size_t prepared_count, const
  * coordinates, on the twist, order r) into a point table, which both the
  * check and the combine read.  Device memory, async on `stream`. */
 #define HBRBC_G2_COMPRESSED_BYTES 96
-/* Bytes of a table of `points` decoded G2 points. */
+/* Bytes of a table of `points` decoded G2 points (table layout: see
+ * hbrbc_g2_prepared_size). */
 size_t hbrbc_g2_points_size(size_t points);
 /* Decodes g2 (count x 192 bytes) into `table` (hbrbc_g2_points_size(count)
  * bytes): affine coordinates and a status per point (invalid points are kept
