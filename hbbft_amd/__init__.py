@@ -178,6 +178,10 @@ def lib():
         "hbrbc_g2_mul_prepared": (ctypes.c_int, [_P, _S, _P, _P, _S, _P, _S, _P, _P, _P, _P, _P]),
         "hbrbc_fr_poly_eval": (ctypes.c_int, [_P, _S, _P, _P, _S, _P, _P, _S, _P, _P, _P]),
         "hbrbc_fr_dot": (ctypes.c_int, [_P, _P, _P, _S, _S, _P, _P, _P]),
+        "hbrbc_hash_g2_batch": (ctypes.c_int, [_P, _P, _S, _S, _P, _P, _P, _P, _P, _P]),
+        "hbrbc_hash_g1_g2_batch": (ctypes.c_int, [_P, _P, _P, _S, _S, _P, _P, _P, _P, _P, _P]),
+        "hbrbc_xor_with_hash_workspace_size": (_S, [_S]),
+        "hbrbc_xor_with_hash_batch": (ctypes.c_int, [_P, _P, _P, _S, _S, _P, _P, _P, _P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -1,6 +1,7 @@
 // api_pairing.hip -- the BLS12-381 entries of include/hbrbc.h: argument checks
 // and launch sequencing over the typed table views of pairing_tables.hpp.
-// Every group and field operation is computed by the kernels in pairing.hip.
+// Every group and field operation is computed by the kernels in pairing.hip
+// (and hash_g2.hip, which is compiled with it).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -504,6 +505,52 @@ int hbrbc_fr_dot(const uint8_t *a, const uint8_t *b, const uint32_t *offsets, si
     if (int rc = have_device()) return rc;
     HB_HIP(launch_fr_dot(a, b, offsets, groups, total, out, status_out,
                          static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
+// ---- hashes and the pad (hash_g2.hip) --------------------------------------
+static int hash_g2_run(const uint8_t *u48, bool with_u, const uint8_t *msgs,
+                       const uint32_t *offsets, size_t count, size_t total, void *out_table,
+                       uint8_t *out192, uint8_t *out96, uint8_t *status_out, uint32_t *words_out,
+                       void *stream) {
+    if (count == 0) return HBRBC_OK;
+    if (!offsets || !out_table || !status_out || (with_u && !u48) || (total && !msgs))
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (total > 0xFFFFFFFFull) return fail(HBRBC_E_INVALID_ARG, "total exceeds 32-bit offsets");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_hash_g2(u48, msgs, offsets, total, view<G2Points>(out_table, count), out192,
+                          out96, status_out, words_out, static_cast<hipStream_t>(stream)));
+    return HBRBC_OK;
+}
+
+int hbrbc_hash_g2_batch(const uint8_t *msgs, const uint32_t *offsets, size_t count, size_t total,
+                        void *out_table, uint8_t *out192, uint8_t *out96, uint8_t *status_out,
+                        uint32_t *words_out, void *stream) {
+    return hash_g2_run(nullptr, false, msgs, offsets, count, total, out_table, out192, out96,
+                       status_out, words_out, stream);
+}
+
+int hbrbc_hash_g1_g2_batch(const uint8_t *u48, const uint8_t *msgs, const uint32_t *offsets,
+                           size_t count, size_t total, void *out_table, uint8_t *out192,
+                           uint8_t *out96, uint8_t *status_out, uint32_t *words_out,
+                           void *stream) {
+    return hash_g2_run(u48, true, msgs, offsets, count, total, out_table, out192, out96,
+                       status_out, words_out, stream);
+}
+
+size_t hbrbc_xor_with_hash_workspace_size(size_t count) { return round_up(count * 32, 256); }
+
+int hbrbc_xor_with_hash_batch(const uint8_t *g48, const uint8_t *data, const uint32_t *offsets,
+                              size_t count, size_t total, uint8_t *out, uint8_t *status_out,
+                              void *workspace, void *stream) {
+    if (count == 0) return HBRBC_OK;
+    if (!g48 || !offsets || !status_out || !workspace || (total && (!data || !out)))
+        return fail(HBRBC_E_INVALID_ARG, "null argument");
+    if (total > 0xFFFFFFFFull) return fail(HBRBC_E_INVALID_ARG, "total exceeds 32-bit offsets");
+    if (int rc = have_device()) return rc;
+    HB_HIP(launch_xor_with_hash(g48, data, offsets, count, total, out, status_out,
+                                static_cast<uint32_t *>(workspace),
+                                static_cast<hipStream_t>(stream)));
     return HBRBC_OK;
 }
 

@@ -44,6 +44,11 @@ G1_X = 0x17f1d3a73197d7942695638c4fa9ac0fc3688c4f9774b905a14e3a3f171bac586c55e83
 G1_Y = 0x08b3f481e3aaa0f1a09e30ed741d8ae4fcf5e095d5d00af600db18cb2c04b3edd03cc744a2888ae40caa232946c5e7e1
 
 
+# the cofactor of E'(Fp2) in the BLS parameter x = -X_ABS (hash_g2.hip)
+H2, _H2_REM = divmod(X_ABS ** 8 + 4 * X_ABS ** 7 + 5 * X_ABS ** 6 - 4 * X_ABS ** 4
+                     - 6 * X_ABS ** 3 - 4 * X_ABS ** 2 + 4 * X_ABS + 13, 9)
+assert _H2_REM == 0 and H2 % 2 == 1
+
 SQRT_EXP = (P - 3) // 4
 SQRT_WINDOWS = (SQRT_EXP.bit_length() + 3) // 4
 
@@ -203,6 +208,12 @@ def main():
         arr("kG1GenQX", mont(gen_q[0])) + "  // Q = [x^2] G1::one() = (beta x, -y): x (y is kG1GenNegY)",
         arr("kG1GenTX", mont(gen_t[0])) + "  // G1::one() + Q, affine x",
         arr("kG1GenTY", mont(gen_t[1])) + "  // G1::one() + Q, affine y",
+        arr("kRand384", pow(2, 406 + 22, P))
+        + "  // 2^428 mod p: fp_mul(v, this) = v 2^22, the Montgomery form of v 2^-384 (hash_g2.hip)",
+        "constexpr uint32_t kH2[16] = {%s};  // the cofactor of E'(Fp2), %d bits"
+        % (", ".join("0x%08xu" % ((H2 >> (32 * i)) & 0xFFFFFFFF) for i in range(16)),
+           H2.bit_length()),
+        "constexpr int kH2Top = %d;  // the cofactor's leading bit" % (H2.bit_length() - 1),
         "}}  // namespace hbrbc::bls",
     ]
     print("\n".join(out))

@@ -2924,4 +2924,8 @@ hipError_t launch_pairing_final(PairWs ws, size_t n_miller, size_t n_out, int pe
     return hipGetLastError();
 }
 
+// hash_g2, hash_g1_g2 and xor_with_hash: kernels and launchers over the units
+// above (this file's anonymous namespace), kept in a file of their own
+#include "hash_g2.hip"
+
 }  // namespace hbrbc

@@ -1,7 +1,7 @@
 // pairing_tables.hpp -- the host layer of pairing.hip: the layout of the
 // prepared point tables and of the workspaces, as typed views, and the launch
 // wrappers that take them.  Internal to libhbrbc.so; included by pairing.hip
-// and api_pairing.hip only.
+// (with hash_g2.hip) and api_pairing.hip only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -141,6 +141,17 @@ hipError_t launch_g1_decompress(const uint8_t *g1c, size_t count, uint8_t *out96
                                 hipStream_t s);
 hipError_t launch_g2_decompress(const uint8_t *g2c, size_t count, uint8_t *out192,
                                 uint8_t *status, hipStream_t s);
+// hashes and the pad (hash_g2.hip, compiled with pairing.hip): hash_g2 of the
+// ragged messages msgs[offsets[i] .. offsets[i + 1]) (with u48: hash_g1_g2, 48
+// bytes per item) into a g2_points table and optionally encoded, the stream
+// words drawn per item (nullable); xor_with_hash of ragged rows with the
+// stream of 48 bytes per row, `seeds` holding 8 words per row
+hipError_t launch_hash_g2(const uint8_t *u48, const uint8_t *msgs, const uint32_t *offsets,
+                          size_t total, TableOut<G2Points> out, uint8_t *out192, uint8_t *out96,
+                          uint8_t *status, uint32_t *words, hipStream_t s);
+hipError_t launch_xor_with_hash(const uint8_t *g48, const uint8_t *data, const uint32_t *offsets,
+                                size_t count, size_t total, uint8_t *out, uint8_t *status,
+                                uint32_t *seeds, hipStream_t s);
 
 // ---- share combine: PublicKeySet::decrypt up to g in G1, combine_signatures
 // in G2.  The two differ in table kind, sizes and launchers only:

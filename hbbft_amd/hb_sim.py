@@ -19,9 +19,11 @@ the checker (tests/test_hb_sim.py).
 Data plane.  `subset_sim`'s for the broadcasts and the coins; the decryption
 tables -- ct_state, share_ok of both variants of every node's share, the
 plaintext -- are forced (Instance) or `decrypt_plane` over real keys.
-`hash_g1_g2`, `xor_with_hash` and the bincode of a `Ciphertext` stay with the
-caller (neither can be pinned without the threshold_crypto crate), which is
-why the plaintext and the deserialisation outcomes travel by reference.
+The plane takes a stand-in H per ciphertext and the plaintext and the
+deserialisation outcomes by reference: `hash_g1_g2` and `xor_with_hash` are in
+threshold.py (parity with the threshold_crypto crate unpinned), feeding the
+plane real hashes is a follow-up, and the bincode of a `Ciphertext` stays
+with the caller.
 
 One epoch only: several live `EpochState`s per node (`max_future_epochs`) are
 the host class's; the device runs them one after the other.

@@ -15,8 +15,8 @@ tampered one).  The lookup of the plaintext is exact: `PublicKeySet::decrypt`
 interpolates g = sum lambda_i share_i at zero, every valid share is
 [x_i] U for the point x_i of one polynomial of degree f, so g = [x(0)] U
 whichever more-than-f valid shares a node combines -- and only valid shares
-are combined (threshold_decrypt.rs:192, 204-217).  `hash_g1_g2`,
-`xor_with_hash`, bincode and the encryption of a proposal stay with the
+are combined (threshold_decrypt.rs:192, 204-217).  bincode and
+the encryption of a proposal (threshold.encrypt_batch) stay with the
 caller: `propose` takes the bytes that go into the Subset, and whether bytes
 deserialise (a ciphertext, a contribution) is a flag of the table.
 """

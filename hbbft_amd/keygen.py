@@ -36,9 +36,10 @@ N-node run whose secret key shares feed threshold.create_decryption_shares /
 create_signature_shares.  These kernels branch on scalar bits: they are not
 constant-time.
 
-Encrypting and decrypting rows and values stays with the caller:
-`sec_key.decrypt` (:564-567, :596-599) includes xor_with_hash, a ChaCha
-stream; the functions here take and return Fr scalars as 32 big-endian bytes.
+Encrypting and decrypting rows and values stays with the caller
+(`sec_key.decrypt`, :564-567, :596-599; threshold.py has xor_with_hash and
+hash_g1_g2 to build it from); the functions here take and return Fr scalars as
+32 big-endian bytes.
 So does `BivarPoly::random`.
 Commitment points arrive compressed (48 bytes), as the messages carry them.
 Functions that take node indices form x = idx + 1 and raise ValueError for

@@ -8,9 +8,9 @@ share (`pk.verify_decryption_share(share, ct)`, lines 220-228), both from
     Ciphertext::verify                      e(G1::one(), W) == e(U, H)
     PublicKeyShare::verify_decryption_share e(share, H)     == e(pk_i, W)
 
-with H = hash_g1_g2(U, V), a G2 point the caller computes once per
-ciphertext (SHA3-256 and a ChaCha-seeded G2 sample -- host work, not on the
-bulk path).  In an epoch every node verifies N shares of each of N
+with H = hash_g1_g2(U, V), a G2 point computed once per ciphertext (SHA3-256
+and a ChaCha-seeded G2 sample: `hash_g1_g2` below runs it on the device; the
+check functions take H as a point from whoever computed it).  In an epoch every node verifies N shares of each of N
 ciphertexts, so the pairing checks come in batches of N^2 per node; this
 module runs them through `hbrbc_pairing_check_batch` (hbbft_amd/csrc/
 pairing.hip): one Miller loop per lane, one final exponentiation per check.
@@ -20,9 +20,11 @@ calls `public_key_set().decrypt(shares, &ct)`: the Lagrange interpolation at 0
 of the shares in G1, g = sum lambda_i share_i, followed by xor_with_hash(g, V).
 `decrypt_combine_prepared` computes g for batches of ciphertexts from the same
 prepared table the checks read, so the verified shares never leave the device;
-`decrypt_shares_grouped` is the two steps in one call.  xor_with_hash (like
-hash_g1_g2) stays with the caller; it hashes the compressed encoding of g,
-which comes back beside the uncompressed one.
+`decrypt_shares_grouped` is the two steps in one call.  `xor_with_hash` turns
+g into the plaintext; it hashes the compressed encoding of g, which comes back
+beside the uncompressed one.  `decrypt_ciphertexts_grouped` is the whole of it
+from wire ciphertexts (U, V, W) to plaintexts, and `encrypt_batch` is
+`PublicKey::encrypt` with given scalars.
 
 `ThresholdSign` (threshold_sign.rs), the common coin of `BinaryAgreement`, is
 the third consumer: every received signature share goes through
@@ -34,7 +36,15 @@ and `combine_and_verify_sig` (lines 249-270) interpolates t + 1 valid shares
 at 0 in G2 and checks the result against the master public key; the coin is
 the signature's parity.  `sig_check_prepared` and `sig_combine_prepared` are
 the two steps on device tables, `threshold_sign_grouped` the whole for many
-coins.  H = hash_g2(doc) stays with the caller and arrives as a G2 point.
+coins.  H arrives as a G2 point; `hash_g2` below computes hash_g2(doc) on the
+device.
+
+The three byte <-> group functions (`hash_g2`, `hash_g1_g2`, `xor_with_hash`;
+hbbft_amd/csrc/hash_g2.hip) follow the definition written out in that file and
+in tests/hash_ref.py.  `threshold_crypto` itself is not available to this
+project, so their byte parity with the crate is not pinned, and
+one deviation is stated: a hash whose product with the cofactor is the point at
+infinity (probability about 2^-255) raises here, where the crate draws again.
 
 Points are the crate's uncompressed encodings (G1: 96 bytes, G2: 192 bytes,
 big-endian; see include/hbrbc.h) or, as hbbft's messages carry them, the
@@ -292,11 +302,13 @@ def verify_decryption_shares_grouped(ciphertexts, shares, device=0):
     return out
 
 
-def _verify_grouped(ciphertexts, shares, device, wire=False):
+def _verify_grouped(ciphertexts, shares, device, wire=False, h_rows=None):
     """The work of verify_decryption_shares_grouped: returns (outcomes by
     table row, the input position of each row, the g1_prepare table of the
     shares -- row r holds share order[r]).  `wire`: W, the shares and the key
-    shares arrive compressed (H stays a point)."""
+    shares arrive compressed (H stays a point).  `h_rows` (wire only): the H of
+    every ciphertext as a device tensor uint8 [C, 192] in place of the host
+    bytes (hash_g1_g2_batch leaves them there)."""
     import numpy as np
     torch = _torch()
     dev = "cuda:%d" % device
@@ -306,7 +318,8 @@ def _verify_grouped(ciphertexts, shares, device, wire=False):
         # W decompressed on the device (an invalid one becomes zero bytes,
         # which g2_prepare rejects), then interleaved with H: H_0, W_0, ...
         dw, _ = g2_decompress(_g2_rows([w for _, w in ciphertexts], dev, G2_COMPRESSED_BYTES))
-        d2 = torch.stack([_g2_rows([h for h, _ in ciphertexts], dev), dw], dim=1)
+        dh = h_rows if h_rows is not None else _g2_rows([h for h, _ in ciphertexts], dev)
+        d2 = torch.stack([dh, dw], dim=1)
         d2 = d2.reshape(2 * len(ciphertexts), G2_BYTES)
     else:
         g2 = np.empty((2 * len(ciphertexts), G2_BYTES), np.uint8)
@@ -539,7 +552,7 @@ def decrypt_shares_grouped_wire(ciphertexts, shares, threshold, device=0):
     return _decrypt_shares(ciphertexts, shares, threshold, device, True)
 
 
-def _decrypt_shares(ciphertexts, shares, threshold, device, wire):
+def _decrypt_shares(ciphertexts, shares, threshold, device, wire, h_rows=None):
     """The body of decrypt_shares_grouped and its wire twin."""
     import numpy as np
     torch = _torch()
@@ -547,7 +560,7 @@ def _decrypt_shares(ciphertexts, shares, threshold, device, wire):
     if not shares:
         return [], outs
     okh, order, sprep = _verify_grouped(ciphertexts, [(c, s, pk) for c, _, s, pk in shares],
-                                        device, wire)
+                                        device, wire, h_rows)
     flags = [False] * len(shares)
     valid = [[] for _ in ciphertexts]   # per ciphertext: (node index, table row)
     for r, i in enumerate(order):
@@ -1022,3 +1035,253 @@ def verify_ciphertexts(items, device=0):
     g1, g2 = _pack([(G1_ONE, w, u, h) for u, w, h in items], device)
     ok = pairing_check_batch(g1, g2).cpu().tolist()
     return [v == CHECK_OK for v in ok]
+
+
+# ---- hashes and the pad: hash_g2, hash_g1_g2, xor_with_hash ----
+HASH_OK, HASH_INVALID, HASH_INFINITY = 0, 2, 3
+FAIL_CIPHERTEXT = "invalid ciphertext"
+FAIL_SHARES = "too few valid shares"
+
+
+def _ragged_bytes(items, dev):
+    """Host byte strings as (flat uint8 tensor, offsets int32 [n + 1]) on dev."""
+    import numpy as np
+    torch = _torch()
+    offs = np.zeros(len(items) + 1, np.int64)
+    offs[1:] = np.cumsum([len(x) for x in items])
+    if offs[-1] >= 1 << 31:
+        raise ValueError("more than 2^31 - 1 bytes in one batch")
+    flat = np.frombuffer(b"".join(bytes(x) for x in items), np.uint8)
+    return (torch.from_numpy(flat.copy()).to(dev),
+            torch.from_numpy(offs.astype(np.int32)).to(dev))
+
+
+def _ragged_args(flat, offsets):
+    torch = _torch()
+    assert flat.dtype == torch.uint8 and flat.dim() == 1 and flat.is_contiguous()
+    assert offsets.dtype == torch.int32 and offsets.dim() == 1 and offsets.numel() >= 1
+    assert offsets.is_contiguous() and offsets.device == flat.device
+    return offsets.numel() - 1, flat.numel()
+
+
+def hash_g2_batch(msgs, offsets, us48=None, encode=True, words=False, stream=None):
+    """hash_g2 of the ragged messages msgs[offsets[i] .. offsets[i + 1]) (msgs
+    uint8 [total], offsets int32 [count + 1], one device) or, with us48 uint8
+    [count, 48], hash_g1_g2(U_i, message i).  Returns (table -- the hashes as a
+    g2_points_prepare table of `count` points, which g2_mul_prepared and
+    sig_check_prepared read --, out192 uint8 [count, 192], out96 uint8 [count,
+    96] (both None without `encode`), status uint8 [count]: 0 ok, 2 a range
+    that is reversed or ends past the messages, 3 the point at infinity after
+    the cofactor, words int32 [count] -- the stream words the sampler drew --
+    or None without `words`).  A range is never read outside msgs."""
+    torch = _torch()
+    count, total = _ragged_args(msgs, offsets)
+    dev = msgs.device
+    if us48 is not None:
+        assert us48.dtype == torch.uint8 and us48.shape == (count, G1_COMPRESSED_BYTES)
+        assert us48.is_contiguous() and us48.device == dev
+    _need_gpu()
+    L = lib()
+    tab = torch.empty(max(1, L.hbrbc_g2_points_size(count)), dtype=torch.uint8, device=dev)
+    o192 = o96 = wd = None
+    if encode:
+        o192 = torch.empty((count, G2_BYTES), dtype=torch.uint8, device=dev)
+        o96 = torch.empty((count, G2_COMPRESSED_BYTES), dtype=torch.uint8, device=dev)
+    if words:
+        wd = torch.empty((count,), dtype=torch.int32, device=dev)
+    st = torch.empty((count,), dtype=torch.uint8, device=dev)
+    tail = (offsets.data_ptr(), count, total, tab.data_ptr(),
+            o192.data_ptr() if encode else None, o96.data_ptr() if encode else None,
+            st.data_ptr(), wd.data_ptr() if words else None, _stream(dev, stream))
+    if us48 is None:
+        _check(L.hbrbc_hash_g2_batch(msgs.data_ptr(), *tail))
+    else:
+        _check(L.hbrbc_hash_g1_g2_batch(us48.data_ptr(), msgs.data_ptr(), *tail))
+    return tab, o192, o96, st, wd
+
+
+def _hash_results(o192, o96, st):
+    sth = st.cpu().tolist()
+    if any(s != HASH_OK for s in sth):
+        # status 3 is the stated deviation: the crate would draw again
+        raise ValueError("hash statuses %r (3: the point at infinity after the cofactor)"
+                         % sorted(set(sth)))
+    a, b = o192.cpu().numpy(), o96.cpu().numpy()
+    return [(bytes(a[i]), bytes(b[i])) for i in range(len(sth))]
+
+
+def hash_g2(docs, device=0):
+    """`hash_g2(doc)` for a list of byte strings: [(H uncompressed 192 bytes, H
+    compressed 96 bytes)].  For device tensors see hash_g2_batch."""
+    if not docs:
+        return []
+    _need_gpu()
+    _, o192, o96, st, _ = hash_g2_batch(*_ragged_bytes(docs, "cuda:%d" % device))
+    return _hash_results(o192, o96, st)
+
+
+def hash_g1_g2(us48, vs, device=0):
+    """`hash_g1_g2(U, V)` for lists of compressed U (48 bytes, hashed as they
+    are: no point is decoded) and byte strings V: [(H192, H96)]."""
+    if len(us48) != len(vs):
+        raise ValueError("%d U for %d V" % (len(us48), len(vs)))
+    for u in us48:
+        if len(u) != G1_COMPRESSED_BYTES:
+            raise ValueError("U of %d bytes, expected %d" % (len(u), G1_COMPRESSED_BYTES))
+    if not vs:
+        return []
+    _need_gpu()
+    dev = "cuda:%d" % device
+    u = _g1_rows(us48, dev, G1_COMPRESSED_BYTES)
+    _, o192, o96, st, _ = hash_g2_batch(*_ragged_bytes(vs, dev), us48=u)
+    return _hash_results(o192, o96, st)
+
+
+def xor_with_hash_batch(gs48, data, offsets, out=None, stream=None):
+    """`xor_with_hash(g_i, row i)` for ragged rows data[offsets[i] .. offsets[i
+    + 1]) (data uint8 [total], offsets int32 [count + 1], ascending) and gs48
+    uint8 [count, 48], the compressed encoding of each g.  Returns (out uint8
+    [total] -- `out` if given, which may be `data` --, status uint8 [count]: 0
+    ok, 2 a range that is reversed or ends past the data, left untouched).
+    Its own inverse; one lane per 16 bytes of a row."""
+    torch = _torch()
+    count, total = _ragged_args(data, offsets)
+    dev = data.device
+    assert gs48.dtype == torch.uint8 and gs48.shape == (count, G1_COMPRESSED_BYTES)
+    assert gs48.is_contiguous() and gs48.device == dev
+    if out is None:
+        out = torch.empty_like(data)
+    assert out.dtype == torch.uint8 and out.shape == data.shape and out.is_contiguous()
+    assert out.device == dev
+    _need_gpu()
+    L = lib()
+    ws = torch.empty(max(1, L.hbrbc_xor_with_hash_workspace_size(count)), dtype=torch.uint8,
+                     device=dev)
+    st = torch.empty((count,), dtype=torch.uint8, device=dev)
+    _check(L.hbrbc_xor_with_hash_batch(gs48.data_ptr(), data.data_ptr(), offsets.data_ptr(),
+                                       count, total, out.data_ptr(), st.data_ptr(),
+                                       ws.data_ptr(), _stream(dev, stream)))
+    return out, st
+
+
+def _split(flat, items):
+    raw, out, pos = bytes(flat.cpu().numpy()), [], 0
+    for x in items:
+        out.append(raw[pos:pos + len(x)])
+        pos += len(x)
+    return out
+
+
+def xor_with_hash(gs48, datas, device=0):
+    """`xor_with_hash(g, data)` for lists of compressed g (48 bytes) and byte
+    strings: the list of padded byte strings."""
+    if len(gs48) != len(datas):
+        raise ValueError("%d g for %d rows" % (len(gs48), len(datas)))
+    if not datas:
+        return []
+    _need_gpu()
+    dev = "cuda:%d" % device
+    flat, offs = _ragged_bytes(datas, dev)
+    out, _ = xor_with_hash_batch(_g1_rows(gs48, dev, G1_COMPRESSED_BYTES), flat, offs)
+    return _split(out, datas)
+
+
+def _scalar_rows(scalars, dev):
+    import numpy as np
+    a = np.frombuffer(b"".join(bytes(s) for s in scalars), np.uint8).reshape(-1, FR_BYTES)
+    return _torch().from_numpy(a.copy()).to(dev)
+
+
+def encrypt_batch(pk, messages, r_scalars, device=0):
+    """`PublicKey::encrypt(msg)` with the scalar r given (the crate draws it):
+    pk = the public key, compressed G1 (48 bytes); r_scalars = one 32-byte
+    big-endian scalar in [1, r) per message.  U = [r] G1::one(), V =
+    xor_with_hash([r] pk, msg), W = [r] hash_g1_g2(U, V): five launches for the
+    batch, and neither [r] pk nor H leaves the device.  Returns [(U compressed
+    48 bytes, V, W compressed 96 bytes)] -- a Ciphertext's fields in wire form.
+    Raises ValueError on a pk that does not decode or a scalar that is zero or
+    >= r.  Not constant-time: for simulations and test networks."""
+    torch = _torch()
+    if len(pk) != G1_COMPRESSED_BYTES:
+        raise ValueError("public key of %d bytes, expected %d" % (len(pk), G1_COMPRESSED_BYTES))
+    if len(messages) != len(r_scalars):
+        raise ValueError("%d scalars for %d messages" % (len(r_scalars), len(messages)))
+    for x in r_scalars:
+        if len(x) != FR_BYTES:
+            raise ValueError("scalar of %d bytes, expected %d" % (len(x), FR_BYTES))
+    if not messages:
+        return []
+    _need_gpu()
+    dev = "cuda:%d" % device
+    n = len(messages)
+    r = _scalar_rows(r_scalars, dev)
+    L = lib()
+    # U = [r] G1::one()
+    utab = torch.empty(max(1, L.hbrbc_g1_prepared_size(n)), dtype=torch.uint8, device=dev)
+    u48 = torch.empty((n, G1_COMPRESSED_BYTES), dtype=torch.uint8, device=dev)
+    ust = torch.empty((n,), dtype=torch.uint8, device=dev)
+    _check(L.hbrbc_g1_base_mul(r.data_ptr(), n, utab.data_ptr(), None, u48.data_ptr(),
+                               ust.data_ptr(), _stream(torch.device(dev), None)))
+    # g = [r] pk, compressed: the pad's key
+    pktab = g1_prepare_compressed(_g1_rows([pk], dev, G1_COMPRESSED_BYTES))
+    zeros = torch.zeros((n,), dtype=torch.int32, device=dev)
+    _, _, g48, gst = g1_mul_prepared(pktab, 1, zeros, r)
+    flat, offs = _ragged_bytes(messages, dev)
+    v, _ = xor_with_hash_batch(g48, flat, offs)
+    # W = [r] hash_g1_g2(U, V), H read from its table
+    htab, _, _, hst, _ = hash_g2_batch(v, offs, us48=u48, encode=False)
+    _, _, w96, wst = g2_mul_prepared(htab, n, torch.arange(n, dtype=torch.int32, device=dev), r)
+    for what, st in (("U", ust), ("[r] pk", gst), ("H", hst), ("W", wst)):
+        bad = sorted(set(st.cpu().tolist()) - {0})
+        if bad:
+            raise ValueError("encrypt: %s has statuses %r" % (what, bad))
+    uh, wh = u48.cpu().numpy(), w96.cpu().numpy()
+    return [(bytes(uh[i]), vi, bytes(wh[i])) for i, vi in enumerate(_split(v, messages))]
+
+
+def decrypt_ciphertexts_grouped(ciphertexts, shares, threshold, device=0):
+    """ThresholdDecrypt from wire ciphertexts to plaintexts: ciphertexts = [(U
+    compressed 48 bytes, V, W compressed 96 bytes)], shares = [(ciphertext
+    index, node index, share G1 compressed, pk_share G1 compressed)].  H =
+    hash_g1_g2(U, V) is computed on the device and stays there;
+    `Ciphertext::verify` is checked with it; the shares are verified and
+    combined as in decrypt_shares_grouped_wire; xor_with_hash(g, V) gives the
+    plaintext.  Returns (bools in the order of `shares`, per ciphertext the
+    plaintext bytes, or FAIL_CIPHERTEXT for one that fails its own check, or
+    FAIL_SHARES with fewer than threshold + 1 valid shares)."""
+    torch = _torch()
+    for u, _, w in ciphertexts:
+        if len(u) != G1_COMPRESSED_BYTES or len(w) != G2_COMPRESSED_BYTES:
+            raise ValueError("ciphertext with U of %d and W of %d bytes" % (len(u), len(w)))
+    if not ciphertexts:
+        return [False] * len(shares), []
+    _need_gpu()
+    dev = "cuda:%d" % device
+    u48 = _g1_rows([u for u, _, _ in ciphertexts], dev, G1_COMPRESSED_BYTES)
+    vs = [v for _, v, _ in ciphertexts]
+    flat, offs = _ragged_bytes(vs, dev)
+    _, h192, _, hst, _ = hash_g2_batch(flat, offs, us48=u48)
+    if any(s != HASH_OK for s in hst.cpu().tolist()):
+        raise ValueError("hash_g1_g2 at infinity after the cofactor")
+    # Ciphertext::verify: e(G1::one(), W) == e(U, H), points decompressed here
+    n = len(ciphertexts)
+    u96, _ = g1_decompress(u48)
+    w192, _ = g2_decompress(_g2_rows([w for _, _, w in ciphertexts], dev, G2_COMPRESSED_BYTES))
+    one = torch.frombuffer(bytearray(G1_ONE), dtype=torch.uint8).to(dev).expand(n, G1_BYTES)
+    g1 = torch.stack([one, u96], dim=1).reshape(2 * n, G1_BYTES).contiguous()
+    g2 = torch.stack([w192, h192], dim=1).reshape(2 * n, G2_BYTES).contiguous()
+    ct_ok = [c == CHECK_OK for c in pairing_check_batch(g1, g2).cpu().tolist()]
+    for _, _, share, pk in shares:
+        for x in (share, pk):
+            if len(x) != G1_COMPRESSED_BYTES:
+                raise ValueError("G1 encoding of %d bytes, expected %d"
+                                 % (len(x), G1_COMPRESSED_BYTES))
+    flags, gs = _decrypt_shares([(None, w) for _, _, w in ciphertexts], shares, threshold, device,
+                                True, h_rows=h192)
+    outs = [FAIL_SHARES if ok else FAIL_CIPHERTEXT for ok in ct_ok]
+    todo = [c for c in range(n) if ct_ok[c] and gs[c] is not None]
+    if todo:
+        plain = xor_with_hash([gs[c][1] for c in todo], [vs[c] for c in todo], device)
+        for c, m in zip(todo, plain):
+            outs[c] = m
+    return flags, outs

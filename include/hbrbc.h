@@ -427,16 +427,17 @@ int hbrbc_unframe_fused(const hbrbc_ctx *ctx, size_t shard_len, size_t payload_s
  * compression/sort flags, points off the curve and points outside the
  * order-r subgroup are rejected per item, as the crate's deserialisation
  * (`into_affine`) rejects them.
- * hash_g1_g2 (SHA3 + ChaCha-seeded G2 sampling, once per ciphertext) stays
- * with the caller, which passes the G2 point.
+ * These entries take H = hash_g1_g2(U, V) as a G2 point; hbrbc_hash_g1_g2_batch
+ * ("hashes and the pad" below) computes it on the device.
  *   `PublicKeySet::decrypt`               (threshold_decrypt.rs:232-252, try_output)
  *       g = sum_i lambda_i share_i, the Lagrange interpolation at 0 of more
  *       than num_faulty valid shares in G1 (x_i = node index + 1, lambda_i =
  *       prod_{j != i} x_j / (x_j - x_i) in the scalar field Fr), from the
  *       shares as hbrbc_g1_prepare left them on the device; the
  *       hbrbc_lagrange_coeffs .. hbrbc_decrypt_combine entries below.
- *       xor_with_hash(g, V), which turns g into the plaintext, stays with the
- *       caller like hash_g1_g2; it hashes the compressed encoding of g. */
+ *       xor_with_hash(g, V), which turns g into the plaintext, is
+ *       hbrbc_xor_with_hash_batch below; it hashes the compressed encoding of
+ *       g. */
 #define HBRBC_G1_BYTES 96
 #define HBRBC_G2_BYTES 192
 #define HBRBC_GT_BYTES 576
@@ -568,8 +569,8 @@ int hbrbc_decrypt_combine(const uint8_t *shares, const uint32_t *idx, size_t n, 
  * sender_idx + 1)` (:603), `generate` sums `commit.row(0)` over the complete
  * parts (:516-534), and `PublicKeySet::public_key_share(i)` is
  * `commit.evaluate(i + 1)`: G1 polynomials evaluated at small integers, and
- * comparisons with [s] G1::one().  Decrypting rows and values (`xor_with_hash`)
- * stays with the caller; scalars arrive as Fr.  Device memory, async on
+ * comparisons with [s] G1::one().  Decrypting rows and values (`sec_key.decrypt`,
+ * over hbrbc_xor_with_hash_batch) stays with the caller; scalars arrive as Fr.  Device memory, async on
  * `stream`; neither entry reads anything back.
  *
  * Evaluates ragged polynomials over a table T of hbrbc_g1_prepare with
@@ -607,8 +608,8 @@ int hbrbc_g1_base_mul_check(const void *a_prepared, size_t prepared_count, const
  * (:216-225, H = hash_g2(doc)) and, with more than num_faulty valid shares,
  * runs `combine_signatures` -- the Lagrange interpolation at 0 of the shares
  * in G2 -- and checks the result against the master public key (:249-270) in
- * the same form.  hash_g2 (a ChaCha-seeded G2 sample) stays with the caller,
- * like hash_g1_g2: H arrives as a G2 point.  Shares arrive in the uncompressed
+ * the same form.  H arrives as a G2 point (hbrbc_hash_g2_batch below computes
+ * hash_g2 on the device).  Shares arrive in the uncompressed
  * encoding (192 bytes) here, or as 96-byte wire shares through
  * hbrbc_g2_points_prepare_compressed below.
  *
@@ -707,8 +708,10 @@ int hbrbc_g2_decompress(const uint8_t *g2c, size_t count, uint8_t *out192, uint8
  * `stream`; no entry reads anything back.  The multiplications branch on the
  * bits of the scalar: they are NOT constant-time and are meant for simulation
  * and test networks, not for a node whose secret key an observer could time.
- * hash_g1_g2, hash_g2, xor_with_hash, `pk.encrypt` / `sec_key.decrypt` of rows
- * and values, and `BivarPoly::random` stay with the caller.
+ * hash_g1_g2, hash_g2 and xor_with_hash have entries of their own below
+ * ("hashes and the pad"); `pk.encrypt` / `sec_key.decrypt` of rows and values
+ * are built from them by the caller, and `BivarPoly::random` stays with the
+ * caller.
  *
  * [s_i] G1::one() for i < count: result i goes to `out_table`
  * (hbrbc_g1_prepared_size(count) bytes) as entry i of a hbrbc_g1_prepare table
@@ -764,6 +767,52 @@ int hbrbc_fr_poly_eval(const uint8_t *scalars, size_t nscalars, const int32_t *r
  * `Poly::interpolate(..).evaluate(0)` of `generate`. */
 int hbrbc_fr_dot(const uint8_t *a, const uint8_t *b, const uint32_t *offsets, size_t groups,
                  size_t total, uint8_t *out, uint8_t *status_out, void *stream);
+
+/* ---- hashes and the pad: bytes to group elements and back -----------------
+ * `threshold_crypto`'s hash_g2(doc) (the H of a signature, the coin's nonce),
+ * hash_g1_g2(U, V) (the H of a ciphertext) and xor_with_hash(g, V) (the pad of
+ * encrypt and decrypt).  The crate is not available to this project: the
+ * definition is the one written out in hbbft_amd/csrc/hash_g2.hip and
+ * tests/hash_ref.py (SHA3-256 seed, ChaCha20 word stream, rejection-sampled
+ * Fq2 x, root y by a drawn flag, the full 507-bit cofactor of E'(Fp2)), and
+ * its byte parity with the crate is NOT pinned.  One stated
+ * deviation: a product with the cofactor at infinity (probability ~2^-255) is
+ * status 3 here; the crate draws again.
+ *
+ * Ragged input: item i is msgs[offsets[i] .. offsets[i + 1]) (offsets: count +
+ * 1 uint32 entries), `total` the bytes in msgs (<= 2^32 - 1); an item whose
+ * range is reversed or ends past `total` is status 2 and nothing of it is
+ * read.  hbrbc_hash_g1_g2_batch appends the 48 bytes at u48 + 48 i (a
+ * ciphertext's U as it arrives on the wire; the bytes are hashed, not read as
+ * a point) to the message, or to its SHA3-256 when it is longer than 64 bytes.
+ * Result i goes to `out_table` (hbrbc_g2_points_size(count) bytes) as entry i
+ * of a hbrbc_g2_points_prepare table over `count` points, bit for bit -- so
+ * hbrbc_g2_mul_prepared and hbrbc_sig_check_prepared read it, and
+ * hbrbc_g2_prepare makes Miller lines of out192 -- and, where the pointers are
+ * non-null, to out192 + 192 i and out96 + 96 i.  status_out[i]: 0 ok, 2 an
+ * invalid description (zero bytes), 3 the point at infinity after the
+ * cofactor.  words_out[i] (nullable): the stream words the sampler drew (25
+ * per attempt, 12 more per rejected Fq draw).  Device memory, async on
+ * `stream`; two launches, nothing is read back. */
+int hbrbc_hash_g2_batch(const uint8_t *msgs, const uint32_t *offsets, size_t count, size_t total,
+                        void *out_table, uint8_t *out192, uint8_t *out96, uint8_t *status_out,
+                        uint32_t *words_out, void *stream);
+int hbrbc_hash_g1_g2_batch(const uint8_t *u48, const uint8_t *msgs, const uint32_t *offsets,
+                           size_t count, size_t total, void *out_table, uint8_t *out192,
+                           uint8_t *out96, uint8_t *status_out, uint32_t *words_out,
+                           void *stream);
+/* xor_with_hash: row i is data[offsets[i] .. offsets[i + 1]) (ranges as above,
+ * offsets ascending), XORed with the low bytes of the stream words of
+ * SHA3-256(g48 + 48 i) -- the compressed encoding of g -- into the same range
+ * of `out` (out may be data; bytes outside the rows are not touched).  Its own
+ * inverse.  One lane per 16 bytes of a row, so long rows spread over the
+ * device.  status_out[i]: 0 ok, 2 an invalid range (neither read nor
+ * written).  workspace >= hbrbc_xor_with_hash_workspace_size(count) bytes.
+ * Device memory, async on `stream`; nothing is read back. */
+size_t hbrbc_xor_with_hash_workspace_size(size_t count);
+int hbrbc_xor_with_hash_batch(const uint8_t *g48, const uint8_t *data, const uint32_t *offsets,
+                              size_t count, size_t total, uint8_t *out, uint8_t *status_out,
+                              void *workspace, void *stream);
 
 /* ---- the Broadcast state machine, batched --------------- */
 /* Many instances x nodes of `Broadcast` (broadcast.rs:228-558) in synchronous
@@ -1023,8 +1072,9 @@ int hbrbc_subset_round(const hbrbc_subset_args *args, void *stream);
  * and share_ok holds `verify_decryption_share` of both variants against the
  * ciphertext of each root slot (g = sum lambda_i share_i does not depend on
  * which f + 1 valid shares are combined, so the plaintext is the slot's).
- * hash_g1_g2, xor_with_hash and the bincode of a Ciphertext stay with the
- * caller, hence ct_state and undeserialisable are inputs.  Fault records:
+ * The simulation takes the outcome of Ciphertext::verify and of the bincode
+ * of a Ciphertext from the caller (the hashes have entries of their own,
+ * hbrbc_hash_g1_g2_batch), hence ct_state and undeserialisable are inputs.  Fault records:
  * blamed node << 8 | kind (enum hbrbc_hb_fault). */
 enum hbrbc_hb_role {            /* per instance and node: the decryption layer's sending side */
     HBRBC_HB_HONEST = 0,
