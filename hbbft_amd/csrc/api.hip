@@ -248,15 +248,11 @@ struct hbrbc_ctx {
         int r_lo, r_hi;
         hipModule_t mod;
         hipFunction_t fn, fe;        // kernel / frame+encode twin (encoder only)
-        // LDS-staged form (jit.hip gen_xor_kernel_lds): its waves share the
-        // stage's input planes, so it cannot run pass by pass
-        bool lds = false;
     };
     // encoder modules by code-object row block (256 = plain layout); an
     // empty vector records a failed load
     std::map<int, std::vector<SpecGroup>> enc_spec;
     int rt_spec = 2;              // output rows per pass of the specialised kernels
-    int depth_spec = 4;           // their input-row prefetch depth
     std::string enc_kind = "none";
     // pattern-specialised decoders: at most one per code-object row block
     struct DecSpec {
@@ -271,10 +267,6 @@ struct hbrbc_ctx {
     };
     std::map<int, DecSpec> dec_spec;
     std::string jit_missing;   // HBRBC_JIT=load: why an encoder code object is missing
-    // side streams + events for the concurrent launch of a matrix's programs
-    // (HBRBC_XOR_STREAMS, launch_groups)
-    std::vector<hipStream_t> side;
-    std::vector<hipEvent_t> side_ev;
     DevBuf d_matrix, d_enc_coefs, d_enc_in, d_enc_out;
     // reconstruct workspace: decode-matrix cache + per-call scratch
     size_t ws_count = 0;
@@ -476,8 +468,8 @@ int run_merkle(hbrbc_ctx *c, const uint8_t *shards, size_t shard_len, const RowM
 
 hipError_t launch_xor_group(const hbrbc_ctx::SpecGroup &g, bool fused, int rt, XorArgs a,
                             size_t count, hipStream_t s);
-hipError_t launch_groups(hbrbc_ctx *c, const std::vector<hbrbc_ctx::SpecGroup> &gs, size_t first,
-                         int rt, const XorArgs &x, size_t count, hipStream_t s);
+hipError_t launch_groups(const std::vector<hbrbc_ctx::SpecGroup> &gs, size_t first, int rt,
+                         const XorArgs &x, size_t count, hipStream_t s);
 
 // Fused unframe (decode paths): the generic reconstruct kernel writes the
 // payload bytes of the data rows it reads or rebuilds, so unframe's re-read of
@@ -589,14 +581,13 @@ int run_reconstruct(hbrbc_ctx *c, uint8_t *shards, size_t shard_len, const RowMa
         x.pat = c->ws_pat.as<int>();
         x.slot_hash = reinterpret_cast<const unsigned long *>(c->pc_hash.as<uint64_t>());
         x.hash_slots = c->pc_cap;
-        x.p_only = -1;
         x.S = (unsigned)shard_len;
         if (uf_payload) {       // fused unframe in the pattern decoders too (_uf variant)
             x.uf_payload = uf_payload;
             x.uf_stride = uf_stride;
             x.uf_status = status;
         }
-        HB_HIP(launch_groups(c, uf_payload ? ds->second.uf_groups : ds->second.groups, 0,
+        HB_HIP(launch_groups(uf_payload ? ds->second.uf_groups : ds->second.groups, 0,
                              ds->second.rt, x, count, s));
     }
     GfApplyArgs g{};
@@ -647,53 +638,19 @@ std::string jit_dir() {
 }
 
 std::string jit_file(const std::string &dir, const std::string &kernel) {
-    const char *aux = getenv("HBRBC_ST_AUX");   // A/B builds get their own files
-    return dir + "/" + kernel + (aux && std::strcmp(aux, "2") ? std::string("_a") + aux : std::string()) +
-           "_v23.co";   // v23: the reconstruct programs store whole 16-byte payload chunks only
+    // v24: the kernels lost their p_only argument; an older object would take
+    // the launcher's arguments at the wrong offsets
+    return dir + "/" + kernel + "_v24.co";
 }
 
 // Input rows in flight of the specialised kernels (HBM latency at 2 waves/SIMD).
-int spec_depth() {
-    if (const char *e = getenv("HBRBC_JIT_DEPTH")) return std::max(1, std::min(8, atoi(e)));
-    return 4;
-}
-
-// Payload rows in flight of the frame+encode twins (36 loaded bytes per row
-// and lane).  HBRBC_JIT_FDEPTH overrides (A/B).
-int spec_fdepth() {
-    if (const char *e = getenv("HBRBC_JIT_FDEPTH")) return std::max(1, std::min(8, atoi(e)));
-    return 2;
-}
-
-// Data-row stores of the frame+encode twins spread over the passes
-// (HBRBC_JIT_SPREAD=0: all in pass 0, A/B).
-bool spec_spread() {
-    const char *e = getenv("HBRBC_JIT_SPREAD");
-    return !(e && !std::strcmp(e, "0"));
-}
-
-// Lane byte positions of the specialised kernels as two 16-byte pieces 1 KB
-// apart: every load and store instruction covers 1 KB of consecutive bytes
-// (cfg3 frame+encode 4.82 -> 4.36 ms against 32 consecutive bytes per lane;
-// HBRBC_JIT_SPLIT=0 builds those, A/B).
-bool spec_split() {
-    const char *e = getenv("HBRBC_JIT_SPLIT");
-    return !(e && !std::strcmp(e, "0"));
-}
-
-// Lockstep interval (input rows between workgroup barriers) of the
-// specialised kernels; 0 = none.  HBRBC_JIT_SYNC overrides (A/B).
-int spec_sync() {
-    if (const char *e = getenv("HBRBC_JIT_SYNC")) return std::max(0, std::min(64, atoi(e)));
-    return 0;
-}
+constexpr int kSpecDepth = 4;
 
 // LDS-staged specialised kernels (jit.hip gen_xor_kernel_lds): every input
-// framed and transposed once per workgroup.  Default for 16..32 input rows
+// framed and transposed once per workgroup.  From 16 input and 14 output rows
 // (cfg3, k = 22: frame+encode 4.25 -> 3.70 ms on one box, r3 A/B in
-// profiles/r3_enc_variants.txt); HBRBC_JIT_LDS=0/1 overrides (A/B).
+// profiles/r3_enc_variants.txt).
 bool spec_lds(size_t nin, size_t nout) {
-    if (const char *e = getenv("HBRBC_JIT_LDS")) return !std::strcmp(e, "1");
     // cfg4 (k = 44): encode 4.41 -> 2.92 ms; cfg5 (k = 84, four programs):
     // encode 12.11 -> 9.89, worst-case reconstruct 11.28 -> 9.08 ms (r3 A/B)
     return nin >= 16 && nout >= 14;
@@ -713,51 +670,25 @@ bool spec_xcd(size_t nin, bool encoder) {
     return encoder && (nin <= 32 || nin >= 64);
 }
 
-// XOR-network form: 0 auto, 1 pairwise, 2 nibble-subset (HBRBC_JIT_NET, A/B).
-int spec_net() {
-    if (const char *e = getenv("HBRBC_JIT_NET")) return std::max(0, std::min(2, atoi(e)));
-    return 0;
-}
-
-// LDS stage size (inputs per stage) and waves/SIMD target of the LDS form
-// (HBRBC_JIT_LDS_STAGE, HBRBC_JIT_WPE; A/B).
-int spec_lds_stage() {
-    if (const char *e = getenv("HBRBC_JIT_LDS_STAGE")) return std::max(1, std::min(32, atoi(e)));
-    return 0;
-}
 // waves/SIMD the LDS form targets: 7-row passes hold 56 accumulators, so
 // 128 VGPRs (4 waves/SIMD) fit without spills (r3 A/B)
 int spec_row_tile(size_t nin, size_t nout);
 int spec_wpe(size_t nin, size_t nout) {
-    if (const char *e = getenv("HBRBC_JIT_WPE")) return std::max(0, std::min(8, atoi(e)));
     if (!spec_lds(nin, nout)) return 0;
     // <= 8-row passes: 128 VGPRs (4 waves/SIMD); 9..11-row passes: 168 (3)
     return spec_row_tile(nin, nout) <= 8 ? 4 : 3;
 }
 
-// Code-object name suffix of the variant options above (only where they
-// change the generated code: the LDS form needs 2..8 passes).
-std::string spec_suffix(size_t nin, size_t nout, int rt, bool encoder) {
-    const int npass = (int)((nout + rt - 1) / rt);
-    std::string s;
-    if (spec_lds(nin, nout) && npass >= 2 && npass <= 8) {
-        s += "_L";
-        if (spec_lds_stage()) s += std::to_string(spec_lds_stage());
-    }
-    if (spec_xcd(nin, encoder)) s += "_X";
-    if (spec_net()) s += "_n" + std::to_string(spec_net());
-    if (spec_wpe(nin, nout)) s += "_w" + std::to_string(spec_wpe(nin, nout));
-    return s;
-}
-
+// The variant of a program whose rows are set (encoders are `fused`), and
+// the code-object name suffix of what changes the generated code.
 void spec_variant(XorProgram &p) {
     const size_t nin = p.in_rows.size(), nout = p.out_rows.size();
     p.lds = spec_lds(nin, nout);
-    p.lds_stage = spec_lds_stage();
     p.xcd = spec_xcd(nin, p.fused);
-    p.net = spec_net();
     p.wpe = spec_wpe(nin, nout);
-    p.name += spec_suffix(nin, nout, p.rt, p.fused);
+    if (xor_lds_form(p)) p.name += "_L";
+    if (p.xcd) p.name += "_X";
+    if (p.wpe) p.name += "_w" + std::to_string(p.wpe);
 }
 
 bool read_file(const std::string &path, std::vector<char> &out) {
@@ -784,8 +715,7 @@ bool write_file(const std::string &path, const std::vector<char> &code) {
 // per row) plus the planes, pair XORs and load buffers must stay near 200
 // VGPRs (2 waves/SIMD) without spilling.
 int spec_row_tile(size_t nin, size_t nout) {
-    // (passes are balanced: rt is the longest pass; HBRBC_RT_SPEC overrides, A/B)
-    if (const char *e = getenv("HBRBC_RT_SPEC")) return std::max(2, std::min(24, atoi(e)));
+    // (passes are balanced: rt is the longest pass)
     // LDS form: passes no longer transpose their own inputs, so short passes
     // (7 rows, nibble-subset network, <= 128 VGPRs) cost no extra transposes;
     // a one-program matrix with more than 56 outputs takes longer passes so
@@ -809,20 +739,17 @@ int spec_row_tile(size_t nin, size_t nout) {
     return nin * nout > 4096 ? 12 : gf_row_tile((int)nout);
 }
 
-// The encoder program of parity-row group [r_lo, r_hi) for row block rb.
-XorProgram encode_program(size_t k, size_t m, const uint8_t *parity_rows, int rt, int depth,
-                          int r_lo, int r_hi, int rb) {
+// The encoder program of parity-row group [r_lo, r_hi) for row block rb
+// (parity_rows = nullptr: everything but the coefficients, for its name).
+XorProgram encode_program(size_t k, size_t m, const uint8_t *parity_rows, int rt, int r_lo,
+                          int r_hi, int rb) {
     XorProgram p;
-    p.sync = spec_sync();
-    p.fdepth = spec_fdepth();
-    p.spread = spec_spread();
-    p.split = spec_split();
-    p.name = encode_kernel_name(k, m, rt, depth, r_lo, r_hi, rb, p.sync, p.fdepth, p.spread, p.split);
+    p.name = encode_kernel_name(k, m, rt, kSpecDepth, r_lo, r_hi, rb);
     for (size_t j = 0; j < k; ++j) p.in_rows.push_back((int)j);
     for (int r = r_lo; r < r_hi; ++r) p.out_rows.push_back((int)(k + r));
-    p.coefs.assign(parity_rows + (size_t)r_lo * k, parity_rows + (size_t)r_hi * k);
+    if (parity_rows) p.coefs.assign(parity_rows + (size_t)r_lo * k, parity_rows + (size_t)r_hi * k);
     p.rt = rt;
-    p.depth = depth;
+    p.depth = kSpecDepth;
     p.rb = rb;
     p.fused = true;
     spec_variant(p);
@@ -838,27 +765,22 @@ bool decode_programs(const std::vector<uint8_t> &mat, size_t k, size_t n, const 
     if (!recovery_rows(mat, k, n, present, valid, missing, rows)) return false;
     hash = pattern_hash(present, (int)n);
     rt = spec_row_tile(k, missing.size());
-    const int depth = spec_depth();
     const auto groups = xor_groups(k, missing.size(), rt);
     out.clear();
     for (size_t gi = 0; gi < groups.size(); ++gi) {
         XorProgram p;
-        p.sync = spec_sync();
-        p.split = spec_split();
-        p.name = decode_kernel_name(n, hash, rt, depth, groups[gi].first, groups[gi].second, rb,
-                                    p.sync, p.split) + (uf ? "_uf" : "");
+        p.name = decode_kernel_name(n, hash, rt, kSpecDepth, groups[gi].first, groups[gi].second, rb);
         p.in_rows = valid;
         p.out_rows.assign(missing.begin() + groups[gi].first, missing.begin() + groups[gi].second);
         p.coefs.assign(rows.begin() + (size_t)groups[gi].first * k,
                        rows.begin() + (size_t)groups[gi].second * k);
         p.rt = rt;
-        p.depth = depth;
+        p.depth = kSpecDepth;
         p.rb = rb;
         p.guard = hash;
         p.uf_k = uf ? (int)k : 0;       // fused unframe: rebuilt data rows, and
         p.uf_inputs = uf && gi == 0;    // the present ones from the first program
-        if (uf) p.name.resize(p.name.size() - 3);   // variant suffix before "_uf"
-        spec_variant(p);
+        spec_variant(p);                // name: stem, variant suffix, then "_uf"
         if (uf) p.name += "_uf";
         out.push_back(std::move(p));
     }
@@ -879,8 +801,6 @@ int load_program(const XorProgram &p, bool compile, hbrbc_ctx::SpecGroup &g) {
     }
     g.mod = nullptr;
     g.fn = g.fe = nullptr;
-    const int npass = (int)((p.out_rows.size() + p.rt - 1) / p.rt);
-    g.lds = p.lds && npass >= 2 && npass <= 8;   // the test of gen_xor_source
     HB_HIP(hipModuleLoadData(&g.mod, code.data()));
     if (hipModuleGetFunction(&g.fn, g.mod, p.name.c_str()) != hipSuccess ||
         (p.fused && hipModuleGetFunction(&g.fe, g.mod, (p.name + "_fe").c_str()) != hipSuccess)) {
@@ -910,7 +830,7 @@ const std::vector<hbrbc_ctx::SpecGroup> *spec_encoder(hbrbc_ctx *c, int rb) {
         const std::string saved = g_err;
         for (const auto &rg : xor_groups(c->k, c->m, c->rt_spec)) {
             const XorProgram p = encode_program(c->k, c->m, c->matrix.data() + c->k * c->k,
-                                                c->rt_spec, c->depth_spec, rg.first, rg.second, rb);
+                                                c->rt_spec, rg.first, rg.second, rb);
             hbrbc_ctx::SpecGroup g{rg.first, rg.second, nullptr, nullptr, nullptr};
             if (load_program(p, compile, g)) {
                 drop_groups(gs);
@@ -930,111 +850,39 @@ const std::vector<hbrbc_ctx::SpecGroup> *spec_encoder(hbrbc_ctx *c, int rb) {
     return slot.empty() ? nullptr : &slot;
 }
 
-// HBRBC_SPEC_SPLIT=1: launch the specialised kernels pass by pass.
-bool spec_pass_split() {
-    const char *e = getenv("HBRBC_SPEC_SPLIT");
-    return e && !std::strcmp(e, "1");
-}
-
+// One launch of a program over `count` instances: a workgroup per 2 KB chunk
+// of a row, one wave per pass.
 hipError_t launch_xor_group(const hbrbc_ctx::SpecGroup &g, bool fused, int rt, XorArgs a,
                             size_t count, hipStream_t s) {
     a.waves_per_row = (a.row_bytes + 64 * 32 - 1) / (64 * 32);
     const size_t blocks = (size_t)a.waves_per_row * count;
     if (blocks > 0xFFFFFFFFull) return hipErrorInvalidValue;
     const int npass = (g.r_hi - g.r_lo + rt - 1) / rt;
+    // in the order of the generated signature (jit.hip Gen::gen_prologue)
     void *args[] = {&a.base,     &a.inst_stride, &a.shard_stride, &a.block_stride,
                     &a.row_bytes, &a.waves_per_row, &a.payloads,  &a.payload_stride,
                     &a.P,        &a.S,           &a.pat,          &a.slot_hash,
-                    &a.hash_slots, &a.p_only,     &a.uf_payload,   &a.uf_stride,
-                    &a.uf_status};
-    hipFunction_t fn = fused ? g.fe : g.fn;
-    // HBRBC_SPEC_SPLIT applies to the streaming form only: a wave of the LDS
-    // form loads just its share of each stage's inputs
-    if (!spec_pass_split() || g.lds) {
-        a.p_only = -1;
-        const unsigned threads = 64u * (unsigned)xor_waves(npass);
-        return hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, threads, 1, 1, 0, s, args, nullptr);
-    }
-    // one launch per pass, one wave per workgroup: every wave on the chip
-    // runs the same pass's code (the three-pass N = 64 program is 151 KB of
-    // straight-line code, more than the instruction cache a CU pair shares)
-    for (a.p_only = 0; a.p_only < npass; ++a.p_only) {
-        const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, 64u, 1, 1, 0, s, args,
-                                                   nullptr);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+                    &a.hash_slots, &a.uf_payload, &a.uf_stride,    &a.uf_status};
+    const unsigned threads = 64u * (unsigned)xor_waves(npass);
+    return hipModuleLaunchKernel(fused ? g.fe : g.fn, (unsigned)blocks, 1, 1, threads, 1, 1, 0, s,
+                                 args, nullptr);
 }
 
 // The programs of a matrix split over several code objects (N = 250: four
 // groups of output rows) read the same input rows.  Launched one after the
-// other, each streams every instance's inputs from HBM again (cfg5: 1.95x /
-// 2.29x the algorithmic bytes, profiles/pmc_traffic.json); launched
-// concurrently on side streams they walk the instances together, so each
-// input row is fetched once and served to the other programs from L2 /
-// MALL -- in theory; measured flat (cfg5 encode 11.9 vs 12.1 ms, reconstruct
-// 11.2 vs 11.5 ms, r3), so HBRBC_XOR_STREAMS=1 enables it for A/B only.
-bool xor_streams() {   // measured no gain (cfg5 73.7 vs 73.2 GB/s, r3): off by default
-    const char *e = getenv("HBRBC_XOR_STREAMS");
-    return e && !std::strcmp(e, "1");
-}
-
-// HBRBC_XOR_TILE=T (A/B): the programs of a split matrix walk the instances
-// T at a time (all programs over instances [i, i + T), then the next T), so
-// the T instances' input rows stay in the Infinity Cache between programs.
-size_t xor_tile() {
-    const char *e = getenv("HBRBC_XOR_TILE");
-    return e ? (size_t)atoll(e) : 0;
-}
-
-hipError_t launch_groups(hbrbc_ctx *c, const std::vector<hbrbc_ctx::SpecGroup> &gs, size_t first,
-                         int rt, const XorArgs &x, size_t count, hipStream_t s) {
-    const size_t ng = gs.size() - first;
-    if (ng == 0) return hipSuccess;
-    const size_t tile = xor_tile();
-    if (ng > 1 && tile && count > tile) {
-        for (size_t i0 = 0; i0 < count; i0 += tile) {
-            XorArgs y = x;
-            y.base = x.base + i0 * x.inst_stride;
-            if (y.payloads) y.payloads = x.payloads + i0 * x.payload_stride;
-            if (y.pat) y.pat = x.pat + i0;
-            if (y.uf_payload) y.uf_payload = x.uf_payload + i0 * x.uf_stride;
-            if (y.uf_status) y.uf_status = x.uf_status + i0;
-            const size_t cnt = std::min(tile, count - i0);
-            for (size_t i = first; i < gs.size(); ++i) {
-                const hipError_t e = launch_xor_group(gs[i], false, rt, y, cnt, s);
-                if (e != hipSuccess) return e;
-            }
-        }
-        return hipSuccess;
-    }
-    if (ng == 1 || !xor_streams()) {
-        for (size_t i = first; i < gs.size(); ++i) {
-            const hipError_t e = launch_xor_group(gs[i], false, rt, x, count, s);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
-    while (c->side.size() < ng) {
-        hipStream_t q;
-        hipError_t e = hipStreamCreateWithFlags(&q, hipStreamNonBlocking);
+// other on the caller's stream, each streams every instance's inputs from HBM
+// again (cfg5: 1.95x / 2.29x the algorithmic bytes,
+// profiles/pmc_traffic.json).  Launching them concurrently on side streams,
+// so that they walk the instances together and share the inputs in L2 / MALL,
+// measured flat (cfg5 encode 11.9 vs 12.1 ms, reconstruct 11.2 vs 11.5 ms,
+// 73.7 vs 73.2 GB/s, r3), so they run in order.
+hipError_t launch_groups(const std::vector<hbrbc_ctx::SpecGroup> &gs, size_t first, int rt,
+                         const XorArgs &x, size_t count, hipStream_t s) {
+    for (size_t i = first; i < gs.size(); ++i) {
+        const hipError_t e = launch_xor_group(gs[i], false, rt, x, count, s);
         if (e != hipSuccess) return e;
-        c->side.push_back(q);
     }
-    while (c->side_ev.size() < ng + 1) {
-        hipEvent_t ev;
-        hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (e != hipSuccess) return e;
-        c->side_ev.push_back(ev);
-    }
-    hipError_t e = hipEventRecord(c->side_ev[ng], s);   // inputs ready on s
-    for (size_t i = 0; i < ng && e == hipSuccess; ++i) {
-        e = hipStreamWaitEvent(c->side[i], c->side_ev[ng], 0);
-        if (e == hipSuccess) e = launch_xor_group(gs[first + i], false, rt, x, count, c->side[i]);
-        if (e == hipSuccess) e = hipEventRecord(c->side_ev[i], c->side[i]);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s, c->side_ev[i], 0);
-    }
-    return e;
+    return hipSuccess;
 }
 
 std::once_flag g_default_once;
@@ -1084,8 +932,7 @@ int encode_rows(hbrbc_ctx *c, uint8_t *shards, size_t shard_len, const RowMap &r
         x.shard_stride = rows.sst;
         x.block_stride = rows.bst;
         x.row_bytes = (unsigned)round_up(shard_len, 16);
-        x.p_only = -1;
-        HB_HIP(launch_groups(c, *gs, 0, c->rt_spec, x, count, s));
+        HB_HIP(launch_groups(*gs, 0, c->rt_spec, x, count, s));
         return HBRBC_OK;
     }
     if (jit_mode() == JIT_LOAD && c->k * c->m <= 16384)
@@ -1249,7 +1096,6 @@ int hbrbc_coding_new(size_t data_shards, size_t parity_shards, int device, hbrbc
         return st;
     }
     c->rt_spec = spec_row_tile(c->k, c->m);
-    c->depth_spec = spec_depth();
     c->enc_kind = c->m == 0 ? "trivial" : (spec_encoder(c, 256) ? "specialised" : "bitslice");
     if (c->m > 0 && c->enc_kind == "bitslice") {
         if (jit_mode() == JIT_COMPILE && c->k * c->m <= 16384) c->enc_kind = "jit-failed";
@@ -1274,8 +1120,6 @@ void hbrbc_coding_free(hbrbc_ctx *c) {
         b->release();
     c->pin.release();
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->side_ev) (void)hipEventDestroy(e);
-    for (hipStream_t q : c->side) (void)hipStreamDestroy(q);
     for (auto &kv : c->enc_spec) drop_groups(kv.second);
     for (auto &kv : c->dec_spec) {
         drop_groups(kv.second.groups);
@@ -1390,13 +1234,12 @@ int hbrbc_frame_encode_rows(hbrbc_ctx *c, const uint8_t *payloads, size_t payloa
     x.payload_stride = payload_stride;
     x.P = (unsigned)payload_len;
     x.S = (unsigned)shard_len;
-    x.p_only = -1;
     const auto &g0 = gs->front();
     HB_HIP(launch_xor_group(g0, true, c->rt_spec, x, count, s));
     HB_HIP(launch_frame_fixup(payloads, payload_stride, payload_len, shards, shard_len, rows,
                               inst_stride, c->k, (size_t)g0.r_hi, c->d_matrix.as<uint8_t>(), count,
                               s));
-    HB_HIP(launch_groups(c, *gs, 1, c->rt_spec, x, count, s));
+    HB_HIP(launch_groups(*gs, 1, c->rt_spec, x, count, s));
     return HBRBC_OK;
 }
 
@@ -2077,13 +1920,13 @@ int hbrbc_jit_build_encode_rows(size_t data_shards, size_t parity_shards, size_t
     std::vector<uint8_t> mat;
     if (!build_matrix(data_shards, n, mat))
         return fail(HBRBC_E_SINGULAR_MATRIX, "singular Vandermonde top block");
-    const int rt = spec_row_tile(data_shards, parity_shards), depth = spec_depth();
+    const int rt = spec_row_tile(data_shards, parity_shards);
     const int rb = (rows_per_block && rows_per_block < n) ? (int)rows_per_block : 256;
     const auto groups = xor_groups(data_shards, parity_shards, rt);
     if (group >= groups.size()) return fail(HBRBC_E_INVALID_ARG, "group %zu of %zu", group,
                                             groups.size());
     const XorProgram p = encode_program(data_shards, parity_shards,
-                                        mat.data() + data_shards * data_shards, rt, depth,
+                                        mat.data() + data_shards * data_shards, rt,
                                         groups[group].first, groups[group].second, rb);
     std::vector<char> code;
     std::string log;
@@ -2112,12 +1955,8 @@ int hbrbc_jit_encode_file_name(size_t data_shards, size_t parity_shards, size_t 
     if (group >= groups.size()) return fail(HBRBC_E_INVALID_ARG, "group %zu of %zu", group,
                                             groups.size());
     const std::string f =
-        jit_file("", encode_kernel_name(data_shards, parity_shards, rt, spec_depth(),
-                                        groups[group].first, groups[group].second, rb,
-                                        spec_sync(), spec_fdepth(), spec_spread(),
-                                        spec_split()) +
-                     spec_suffix(data_shards, groups[group].second - groups[group].first, rt, true))
-            .substr(1);
+        jit_file("", encode_program(data_shards, parity_shards, nullptr, rt, groups[group].first,
+                                    groups[group].second, rb).name).substr(1);
     if (f.size() + 1 > buf_len) return fail(HBRBC_E_INVALID_ARG, "buffer too small");
     std::memcpy(buf, f.c_str(), f.size() + 1);
     return HBRBC_OK;

@@ -18,24 +18,31 @@
 // coefficient, gen_nibble_network); at 14-row passes its longer live ranges
 // cost occupancy and it measured slower (5.7 -> 9.0 ms, cfg3).
 //
-// Layout and lane mapping are those of gf_bitslice_kernel: a lane owns 32
-// consecutive byte positions of every row; a workgroup holds one wave per
-// pass (up to 8) over the same positions, wave w producing passes w, w+8, ...
-// of rt output rows.  Rows are addressed through one buffer resource per row block (the
+// Layout and lane mapping: a lane owns 32 byte positions of every row, as two
+// 16-byte pieces 1 KB apart inside a 2 KB chunk, so every load and store
+// instruction of a wave covers 1 KB of consecutive bytes (cfg3 frame+encode
+// 4.82 -> 4.36 ms against 32 consecutive bytes per lane, the mapping of
+// gf_bitslice_kernel).  A workgroup holds one wave per pass (up to 8) over
+// the same positions, wave w producing passes w, w+8, ... of rt output rows.
+// Rows are addressed through one buffer resource per row block (the
 // blocked layouts of the validator-sharded simulation, launchers.hpp RowMap)
 // and an SGPR row offset.  Output is bit-identical to the generic kernel
 // (tests compare both with the oracle).
 //
+// Two forms (xor_lds_form): the streaming form, where every wave loads and
+// transposes every input itself, and the LDS form, where each input is
+// transposed once per workgroup.  Both are written with the emitters of Gen.
+//
 // Code objects are cached as files under <lib dir>/jit (names from
-// encode_kernel_name / decode_kernel_name + "_v23.co");
-// __graft_entry__.build() pre-generates the encoders of the BASELINE
-// validator counts and the decoders the bench's fixed patterns need.
+// encode_kernel_name / decode_kernel_name + "_v24.co"; v24: the kernels
+// lost their p_only argument, so older objects no longer match the launcher's
+// argument list); __graft_entry__.build() pre-generates the encoders of the
+// BASELINE validator counts and the decoders the bench's fixed patterns need.
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <set>
 #include <sstream>
 #include <string>
@@ -65,33 +72,21 @@ const char *kPrelude = R"(
 typedef unsigned int uint32_t;
 typedef unsigned char uint8_t;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#ifndef HB_ST_AUX
 #define HB_ST_AUX 2   // cache policy of the row stores: non-temporal (encode 5.7 -> 5.15 ms, cfg3)
-#endif
-// 32 bytes starting `bs` (0..3, wave-uniform) bytes into the 36 loaded bytes
-// (q0, q1, q2[0]): eight v_alignbyte with a scalar shift
-__device__ __forceinline__ void hb_window(const u32x4 q0, const u32x4 q1, const uint32_t q2,
-                                          unsigned bs, uint32_t (&o)[8]) {
-    const uint32_t w[9] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3], q2};
-    _Pragma("unroll") for (int i = 0; i < 8; ++i) o[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], bs);
-}
-// split lanes: two 16-byte windows from 20 loaded bytes each (q, q2)
+// A lane's two 16-byte windows, each starting `bs` (0..3, wave-uniform) bytes
+// into the 20 bytes loaded at its piece (q, q2): eight v_alignbyte with a
+// scalar shift
 __device__ __forceinline__ void hb_window2(const u32x4 qa, const uint32_t qa2, const u32x4 qb,
                                            const uint32_t qb2, unsigned bs, uint32_t (&o)[8]) {
     const uint32_t w[10] = {qa[0], qa[1], qa[2], qa[3], qa2, qb[0], qb[1], qb[2], qb[3], qb2};
     _Pragma("unroll") for (int i = 0; i < 4; ++i) o[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], bs);
     _Pragma("unroll") for (int i = 0; i < 4; ++i) o[4 + i] = __builtin_amdgcn_alignbyte(w[i + 6], w[i + 5], bs);
 }
-// The window of a lane whose 32 framed bytes start at lb < 4, i.e. inside
+// The first window of a lane whose framed bytes start at lb < 4, i.e. inside
 // the 4-byte BE32 length prefix (broadcast.rs:175-177; only offset 0 of rows
 // with j * S < 4): header bytes hdr[lb..3], then payload bytes 0..
-// q0, q1 = payload dwords 0..7 (HB_LDF clamps that lane's load address to 0).
-__device__ __forceinline__ void hb_frame_head(const u32x4 q0, const u32x4 q1, unsigned P,
-                                              unsigned lb, uint32_t (&x)[8]) {
-    const uint32_t w[9] = {__builtin_bswap32(P), q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3]};
-    _Pragma("unroll") for (int i = 0; i < 8; ++i) x[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], lb);
-}
-// split lanes: only the first 16-byte window starts in the prefix
+// qa = payload dwords 0..3 (HB_LDF2 clamps that lane's load address to 0).
+// Only the first window can start in the prefix: the second is 1 KB further.
 __device__ __forceinline__ void hb_frame_head2(const u32x4 qa, unsigned P, unsigned lb, uint32_t (&x)[8]) {
     const uint32_t w[5] = {__builtin_bswap32(P), qa[0], qa[1], qa[2], qa[3]};
     _Pragma("unroll") for (int i = 0; i < 4; ++i) x[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], lb);
@@ -243,240 +238,187 @@ void gen_pair_network(std::ostringstream &o, const CoefView &cv, int t0, int row
         }
 }
 
-// Network of input jj for output rows t0..t0+rows-1 (net: 0 auto, 1 pairwise,
-// 2 nibble-subset).
-void gen_network(std::ostringstream &o, const CoefView &cv, int t0, int rows, size_t jj, int rt,
-                 int net) {
-    if (net == 2 || (net == 0 && rt <= 8))
-        gen_nibble_network(o, cv, t0, rows, jj);
-    else
-        gen_pair_network(o, cv, t0, rows, jj);
-}
+// Payload rows in flight of the streaming frame+encode twin (40 loaded bytes
+// per row and lane); the other kernels take XorProgram::depth.
+constexpr int kFusedDepth = 2;
+// Inputs per stage of the LDS form: 48 KB of LDS per workgroup.  Stages of 12
+// / 16 inputs measured flat, 28 / 32 slower (cfg5 encode 9.40 vs 9.07 ms).
+constexpr int kLdsStage = 24;
 
-// Signature, guard, lane mapping, buffer resources and the load macros shared
-// by both kernel forms.  `fused` = the frame+encode twin.
-void gen_prologue(std::ostringstream &o, const XorProgram &p, bool fused, int npass,
-                  const std::set<int> &blocks, const char *d2, const std::string &lds_decl) {
-    auto blk = [&](int row) { return row / p.rb; };
-    (void)blk;
-    // one wave per pass (up to 8): the waves of a workgroup stream the same
-    // input rows together, so each row comes from HBM about once per program
-    // (4 waves over 6 passes fetched 4.6x the input at cfg5, PMC FETCH_SIZE)
-    o << "\nextern \"C\" __global__ __launch_bounds__(" << xor_waves(npass) * 64 << ") "
-      << (p.wpe > 0 ? "__attribute__((amdgpu_waves_per_eu(" + std::to_string(p.wpe) + "))) " : std::string())
-      << "void "
-      << p.name << (fused ? "_fe" : "")
-      << "(uint8_t *__restrict__ base, unsigned long inst_stride, unsigned long shard_stride,\n"
-         "    unsigned long block_stride, unsigned row_bytes, unsigned waves_per_row,\n"
-         "    const uint8_t *__restrict__ payloads, unsigned long payload_stride, unsigned P, unsigned S,\n"
-         "    const int *__restrict__ pat, const unsigned long *__restrict__ slot_hash, int hash_slots,\n"
-         "    int p_only, uint8_t *__restrict__ uf_payload, unsigned long uf_stride,\n"
-         "    const int *__restrict__ uf_status) {\n"
-      << lds_decl;
-    // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2.
-    // p.xcd: workgroup b takes chunk (b % 8) * (grid / 8) + b / 8, so one XCD
-    // walks consecutive 2 KB chunks of a row: the lines two chunks share (row
-    // starts are 16-byte, not line aligned) and the payload lines their
-    // windows both read meet in one L2 instead of two
-    if (p.xcd)
-        o << "  unsigned bid_ = blockIdx.x;\n"
-             "  { const unsigned per_ = gridDim.x >> 3; if (bid_ < per_ * 8u) bid_ = (bid_ & 7u) * per_ + (bid_ >> 3); }\n";
-    else
-        o << "  const unsigned bid_ = blockIdx.x;\n";
-    o << "  const unsigned long inst = bid_ / waves_per_row;\n";
-    if (p.guard) {
-        // reconstruct of one cached erasure pattern: other patterns return
-        char g[64];
-        snprintf(g, sizeof g, "0x%016llxull", (unsigned long long)p.guard);
-        o << "  { const int sl_ = pat[inst];\n"
-             "    if (sl_ >= hash_slots || slot_hash[sl_] != "
-          << g << ") return; }\n";
-    }
-    // a lane's 32 byte positions: off..off+15 and off2..off2+15.  Default:
-    // 32 consecutive bytes (off2 = off + 16); split: two 16-byte pieces 1 KB
-    // apart, so every load and store instruction of a wave covers 1 KB of
-    // consecutive bytes instead of 64 pieces of 16 with 16-byte gaps
-    o << "  const int wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);\n"
-         "  const unsigned wchunk = bid_ - (unsigned)inst * waves_per_row, lane = threadIdx.x & 63u;\n"
-      << (p.split ? "  unsigned off = wchunk * 2048u + lane * 16u;\n" : "  unsigned off = (wchunk * 64u + lane) * 32u;\n")
-      << "  const bool active = off < row_bytes;\n"
-         "  if (!active) off = row_bytes - 16u;\n"
-         "  const bool full = off + " << d2 << " + 16u <= row_bytes;\n"
-         "  const unsigned off2 = full ? off + " << d2 << " : off;\n"
-         // raw buffer ops: each row block's base lives in a scalar resource,
-         // the row offset (row % rb) * shard_stride in an SGPR (soffset) and
-         // the lane offset in one VGPR -- no per-lane 64-bit address per row
-         "  uint8_t *const ib = base + inst * inst_stride;\n";
-    if (p.uf_k > 0)
-        o << "  uint8_t *const ufp = (uf_payload && uf_status[inst] == 0) ? uf_payload + inst * uf_stride"
-             " : (uint8_t *)0;\n";
-    for (int q : blocks)
-        o << "  const __amdgpu_buffer_rsrc_t rs" << q << " = __builtin_amdgcn_make_buffer_rsrc(ib"
-          << (q ? " + " + std::to_string(q) + "ul * block_stride" : std::string()) << ", (short)0, "
-          << "0x7fffffff, 0x00020000);\n";
-    o << "  const unsigned sst = (unsigned)shard_stride;\n"
-         "#define HB_LD(L, H, Q, R) { L = __builtin_amdgcn_raw_buffer_load_b128(rs##Q, off, (R) * sst, 0); "
-         "H = __builtin_amdgcn_raw_buffer_load_b128(rs##Q, off2, (R) * sst, 0); }\n";
-    if (fused)
-        // framing (broadcast.rs:174-189) folded into the loads: logical byte b
-        // of the framed value is payload byte b - 4.  The buffer resource
-        // covers the whole dwords of the payload (P & ~3 bytes; range checks
-        // are per dword), so everything past them reads 0; the 0-3 bytes of a
-        // partial last dword are added, with their parity, by frame_fixup.
-        o << "  const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(\n"
-             "      (void *)(payloads + inst * payload_stride), (short)0, (int)(P & ~3u), 0x00020000);\n"
-             "  const bool edge = !__all(off + " << d2 << " + 16u <= S);\n"
-             // dword-aligned start: the 32 framed bytes of a lane are bytes
-             // bs..bs+31 of 36 loaded bytes, bs = (j*S - 4) & 3 (uniform per row)
-             // (the address add is volatile asm: LLVM would otherwise hoist every
-             // row's address out of the pass loop and keep k of them live)
-             "#define HB_LDF(Q0, Q1, Q2, j) { unsigned a_; "
-             "__asm__ volatile(\"v_add_u32 %0, %1, %2\" : \"=v\"(a_) : \"s\"((j) * S - 4u), \"v\"(off)); "
-             "a_ &= ~3u; "
-             // a window starting inside the length prefix loads payload dwords 0..8
-             "if ((j) < 4u && (j) * S + off < 4u) a_ = 0u; "
-             "Q0 = __builtin_amdgcn_raw_buffer_load_b128(pr, a_, 0, 0); "
-             "Q1 = __builtin_amdgcn_raw_buffer_load_b128(pr, a_ + 16u, 0, 0); "
-             "Q2 = __builtin_amdgcn_raw_buffer_load_b32(pr, a_ + 32u, 0, 0); }\n"
-             // split lanes: 20 bytes at each of the two pieces
-             "#define HB_LDF2(QA, QA2, QB, QB2, j) { unsigned a_, b_; "
-             "__asm__ volatile(\"v_add_u32 %0, %1, %2\" : \"=v\"(a_) : \"s\"((j) * S - 4u), \"v\"(off)); "
-             "__asm__ volatile(\"v_add_u32 %0, %1, %2\" : \"=v\"(b_) : \"s\"((j) * S - 4u), \"v\"(off2)); "
-             "a_ &= ~3u; b_ &= ~3u; "
-             "if ((j) < 4u && (j) * S + off < 4u) a_ = 0u; "
-             "QA = __builtin_amdgcn_raw_buffer_load_b128(pr, a_, 0, 0); "
-             "QA2 = __builtin_amdgcn_raw_buffer_load_b32(pr, a_ + 16u, 0, 0); "
-             "QB = __builtin_amdgcn_raw_buffer_load_b128(pr, b_, 0, 0); "
-             "QB2 = __builtin_amdgcn_raw_buffer_load_b32(pr, b_ + 16u, 0, 0); }\n";
-}
-
-// One kernel of a program: `fused` = the frame+encode twin.
-std::string gen_xor_kernel(const XorProgram &p, bool fused) {
-    const size_t nin = p.in_rows.size();
-    const int nout = (int)p.out_rows.size();
-    // npass passes of at most rt rows, balanced (42 rows at rt 12: 11, 11,
+// One kernel of a program: what both forms share -- the balanced passes, the
+// prologue, and the emitters of the row loads, of a lane's eight words x[8]
+// and of the row stores.
+struct Gen {
+    const XorProgram &p;
+    const bool fused;   // the frame+encode twin
+    const int nin, nout;
+    // npass passes of at most p.rt rows, balanced (42 rows at rt 12: 11, 11,
     // 10, 10 rather than 12, 12, 12, 6 -- the longest pass sets the time)
-    const int npass = (nout + p.rt - 1) / p.rt;
-    auto pass_lo = [&](int ps) { return ps * (nout / npass) + std::min(ps, nout % npass); };
-    const int rt = (nout + npass - 1) / npass;
-    const int depth = fused ? p.fdepth : p.depth;  // 36 bytes per row in flight when fused
-    const int nbuf = depth + 1;
-    const int rb = p.rb;
-    // every wave runs exactly one pass only when npass <= 8 waves: only then
-    // do all waves reach the same barriers
-    const bool lockstep = p.sync > 0 && npass <= 8 && npass > 1;
-    const CoefView cv{p.coefs.data(), nin};
-    auto blk = [&](int row) { return row / rb; };
-    auto rin = [&](int row) { return row % rb; };
-    std::set<int> blocks;
-    for (int r : p.in_rows) blocks.insert(blk(r));
-    for (int r : p.out_rows) blocks.insert(blk(r));
-    const char *d2 = p.split ? "1024u" : "16u";
+    const int npass;
+    const int rt;       // rows of the longest pass
+    const CoefView cv;
     std::ostringstream o;
-    gen_prologue(o, p, fused, npass, blocks, d2, "");
 
-    // p_only >= 0: this launch runs that one pass with one wave per workgroup
-    // (the host launches the passes one after another, so every wave on a CU
-    // runs the same straight-line code); p_only < 0: wave w runs passes w,
-    // w + nw, ... of the same byte positions
-    o << "  const int p_lo = p_only >= 0 ? p_only : __builtin_amdgcn_readfirstlane(wave);\n"
-         "  const int p_hi = p_only >= 0 ? p_only + 1 : " << npass << ";\n"
-         "  const int p_st = p_only >= 0 ? 1 : nw;\n"
-         "  for (int p = p_lo; p < p_hi; p += p_st) {\n    switch (p) {\n";
-    for (int ps = 0; ps < npass; ++ps) {
-        const int t0 = pass_lo(ps);
-        const int rows = pass_lo(ps + 1) - t0;
-        // a distinct barrier opens every case, so no common prefix (the first
-        // rows' loads) is hoisted above the switch and kept live across it
-        o << "    case " << ps << ": {\n      __asm__ volatile(\"; pass " << ps
-          << "\" ::: \"memory\");\n      uint32_t a[" << rows << "][8] = {};\n";
-        if (fused)
-            // S through an opaque SGPR copy per pass: otherwise every pass's row
-            // offsets (j * S - 4 and its byte shift) are loop-invariant, get
-            // hoisted above the pass loop and spill (41 SGPRs in the cfg3 encoder)
-            o << "      unsigned S_; __asm__ volatile(\"s_mov_b32 %0, %1\" : \"=s\"(S_) : \"s\"(S));\n"
-                 "      const unsigned S = S_;\n"
-                 "      u32x4 q0[" << nbuf << "], q1[" << nbuf << "]; uint32_t q2[" << nbuf << "]"
-              << (p.split ? ", q3[" + std::to_string(nbuf) + "]" : std::string()) << ";\n";
+    Gen(const XorProgram &p_, bool fused_)
+        : p(p_), fused(fused_), nin((int)p_.in_rows.size()), nout((int)p_.out_rows.size()),
+          npass((nout + p_.rt - 1) / p_.rt), rt((nout + npass - 1) / npass),
+          cv{p_.coefs.data(), p_.in_rows.size()} {}
+
+    int pass_lo(int ps) const { return ps * (nout / npass) + std::min(ps, nout % npass); }
+    int blk(int row) const { return row / p.rb; }
+    int rin(int row) const { return row % p.rb; }
+    // the first parity group of an encoder also writes the framed data rows
+    bool writes_data_rows() const { return fused && p.out_rows.front() == nin; }
+
+    // Signature, guard, lane mapping, buffer resources and the load macros.
+    void gen_prologue(const std::string &lds_decl) {
+        // one wave per pass (up to 8): the waves of a workgroup stream the same
+        // input rows together, so each row comes from HBM about once per program
+        // (4 waves over 6 passes fetched 4.6x the input at cfg5, PMC FETCH_SIZE)
+        o << "\nextern \"C\" __global__ __launch_bounds__(" << xor_waves(npass) * 64 << ") "
+          << (p.wpe > 0 ? "__attribute__((amdgpu_waves_per_eu(" + std::to_string(p.wpe) + "))) " : std::string())
+          << "void "
+          << p.name << (fused ? "_fe" : "")
+          << "(uint8_t *__restrict__ base, unsigned long inst_stride, unsigned long shard_stride,\n"
+             "    unsigned long block_stride, unsigned row_bytes, unsigned waves_per_row,\n"
+             "    const uint8_t *__restrict__ payloads, unsigned long payload_stride, unsigned P, unsigned S,\n"
+             "    const int *__restrict__ pat, const unsigned long *__restrict__ slot_hash, int hash_slots,\n"
+             "    uint8_t *__restrict__ uf_payload, unsigned long uf_stride,\n"
+             "    const int *__restrict__ uf_status) {\n"
+          << lds_decl;
+        // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2.
+        // p.xcd: workgroup b takes chunk (b % 8) * (grid / 8) + b / 8, so one XCD
+        // walks consecutive 2 KB chunks of a row: the lines two chunks share (row
+        // starts are 16-byte, not line aligned) and the payload lines their
+        // windows both read meet in one L2 instead of two
+        if (p.xcd)
+            o << "  unsigned bid_ = blockIdx.x;\n"
+                 "  { const unsigned per_ = gridDim.x >> 3; if (bid_ < per_ * 8u) bid_ = (bid_ & 7u) * per_ + (bid_ >> 3); }\n";
         else
-            o << "      u32x4 l[" << nbuf << "], h[" << nbuf << "];\n";
-        auto load = [&](size_t jj) {
-            const int b = (int)(jj % nbuf);
-            const int row = p.in_rows[jj];
-            if (fused && p.split)
-                o << "      HB_LDF2(q0[" << b << "], q2[" << b << "], q1[" << b << "], q3[" << b << "], " << row
-                  << "u)";
-            else if (fused)
-                o << "      HB_LDF(q0[" << b << "], q1[" << b << "], q2[" << b << "], " << row << "u)";
-            else
-                o << "      HB_LD(l[" << b << "], h[" << b << "], " << blk(row) << ", " << rin(row) << "u)";
-            // the empty asm keeps the scheduler from hoisting every row's load to
-            // the top of the straight-line pass (hundreds of live VGPRs)
-            o << " __asm__ volatile(\"\" ::: \"memory\");\n";
-        };
-        // inputs 0..depth-1 in flight before the first product; input jj + depth
-        // is requested while input jj is consumed (depth rows of HBM latency hidden)
-        for (int jj = 0; jj < depth && jj < (int)nin; ++jj) load((size_t)jj);
-        for (size_t jj = 0; jj < nin; ++jj) {
-            const int cur = (int)(jj % nbuf);
-            const int row = p.in_rows[jj];
-            if (jj + depth < nin) load(jj + depth);
-            if (fused) {
-                const std::string c = std::to_string(cur);
-                o << "      { uint32_t x[8];\n";
-                if (p.split)
-                    o << "        hb_window2(q0[" << c << "], q2[" << c << "], q1[" << c << "], q3[" << c
-                      << "], (" << row << "u * S - 4u) & 3u, x);\n";
-                else
-                    o << "        hb_window(q0[" << c << "], q1[" << c << "], q2[" << c << "], (" << row
-                      << "u * S - 4u) & 3u, x);\n";
-                // windows touching the BE32 payload length (broadcast.rs:175-177);
-                // j * S < 4 needs j < 4 since S >= 1
-                if (row < 4)
-                    o << "        if (" << row << "u * S < 4u) { if (off == 0u) "
-                      << (p.split ? "hb_frame_head2(q0[" + c + "], " : "hb_frame_head(q0[" + c + "], q1[" + c + "], ")
-                      << "P, " << row << "u * S, x); }\n";
-                // positions >= S of this row belong to the next shard: zero
-                o << "        if (edge) {\n"
-                     "          _Pragma(\"unroll\") for (int i_ = 0; i_ < 8; ++i_) {\n"
-                     "            const int lim_ = (int)S - (int)(i_ < 4 ? off + 4 * i_ : off2 + 4 * (i_ - 4));\n"
-                     "            x[i_] = lim_ >= 4 ? x[i_] : (lim_ <= 0 ? 0u : x[i_] & (0xFFFFFFFFu >> (8 * (4 - lim_))));\n"
-                     "          }\n        }\n";
-                // group 0 also writes the framed data rows, pass jj % npass row jj
-                // (spread over the waves: a store ahead of a load holds that
-                // load's vmcnt wait, and pass 0 storing all 22 rows at cfg3 made
-                // it the workgroup's slowest wave)
-                if (p.out_rows.front() == (int)nin && (p.spread ? (int)(jj % npass) == ps : ps == 0))
-                    o << "        if (active) {\n"
-                         "          __builtin_amdgcn_raw_buffer_store_b128((u32x4){x[0], x[1], x[2], x[3]}, rs"
-                      << blk(row) << ", off, " << rin(row) << "u * sst, HB_ST_AUX);\n"
-                         "          if (full) __builtin_amdgcn_raw_buffer_store_b128((u32x4){x[4], x[5], x[6], x[7]}, "
-                         "rs" << blk(row) << ", off2, " << rin(row) << "u * sst, HB_ST_AUX);\n        }\n";
-                o << "        hb_tr(x);\n";
-            } else {
-                const std::string lc = "l[" + std::to_string(cur) + "]";
-                o << "      { const u32x4 hh = full ? h[" << cur << "] : (u32x4)(0u);\n"
-                  << "        uint32_t x[8] = {" << lc << "[0], " << lc << "[1], " << lc << "[2], " << lc
-                  << "[3], hh[0], hh[1], hh[2], hh[3]};\n";
-                if (p.uf_k > 0 && p.uf_inputs && ps == 0 && row < p.uf_k)
-                    o << "        if (ufp && active) { hb_uf_put(ufp, S, " << row
-                      << "u, off, x[0], x[1], x[2], x[3]); if (full) hb_uf_put(ufp, S, " << row
-                      << "u, off2, x[4], x[5], x[6], x[7]); }\n";
-                o << "        hb_tr(x);\n";
-            }
-            // short passes: the nibble-subset network (net 0), or as forced
-            gen_network(o, cv, t0, rows, jj, rt, p.net);
-            // pin the accumulators after every input: without this the
-            // reassociation pass flattens each accumulator's whole XOR chain
-            // over all inputs and keeps every input's planes live at once
-            o << "        for (int t_ = 0; t_ < " << rows << "; ++t_) for (int q_ = 0; q_ < 8; ++q_) "
-                 "__asm__ volatile(\"\" : \"+v\"(a[t_][q_]));\n      }\n";
-            // lockstep: the passes of a workgroup meet every `sync` rows, so a
-            // row's bytes are fetched once and served from L1/L2 to the other
-            // waves (a plain s_barrier: the prefetched rows stay in flight)
-            if (lockstep && (jj + 1) % (size_t)p.sync == 0 && jj + 1 < nin)
-                o << "      __builtin_amdgcn_s_barrier();\n";
+            o << "  const unsigned bid_ = blockIdx.x;\n";
+        o << "  const unsigned long inst = bid_ / waves_per_row;\n";
+        if (p.guard) {
+            // reconstruct of one cached erasure pattern: other patterns return
+            char g[64];
+            snprintf(g, sizeof g, "0x%016llxull", (unsigned long long)p.guard);
+            o << "  { const int sl_ = pat[inst];\n"
+                 "    if (sl_ >= hash_slots || slot_hash[sl_] != "
+              << g << ") return; }\n";
         }
+        // a lane's 32 byte positions: off..off+15 and off2..off2+15, 1 KB apart
+        o << "  const int wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6);\n"
+             "  const unsigned wchunk = bid_ - (unsigned)inst * waves_per_row, lane = threadIdx.x & 63u;\n"
+             "  unsigned off = wchunk * 2048u + lane * 16u;\n"
+             "  const bool active = off < row_bytes;\n"
+             "  if (!active) off = row_bytes - 16u;\n"
+             "  const bool full = off + 1024u + 16u <= row_bytes;\n"
+             "  const unsigned off2 = full ? off + 1024u : off;\n"
+             // raw buffer ops: each row block's base lives in a scalar resource,
+             // the row offset (row % rb) * shard_stride in an SGPR (soffset) and
+             // the lane offset in one VGPR -- no per-lane 64-bit address per row
+             "  uint8_t *const ib = base + inst * inst_stride;\n";
+        if (p.uf_k > 0)
+            o << "  uint8_t *const ufp = (uf_payload && uf_status[inst] == 0) ? uf_payload + inst * uf_stride"
+                 " : (uint8_t *)0;\n";
+        std::set<int> blocks;
+        for (int r : p.in_rows) blocks.insert(blk(r));
+        for (int r : p.out_rows) blocks.insert(blk(r));
+        for (int q : blocks)
+            o << "  const __amdgpu_buffer_rsrc_t rs" << q << " = __builtin_amdgcn_make_buffer_rsrc(ib"
+              << (q ? " + " + std::to_string(q) + "ul * block_stride" : std::string()) << ", (short)0, "
+              << "0x7fffffff, 0x00020000);\n";
+        o << "  const unsigned sst = (unsigned)shard_stride;\n"
+             "#define HB_LD(L, H, Q, R) { L = __builtin_amdgcn_raw_buffer_load_b128(rs##Q, off, (R) * sst, 0); "
+             "H = __builtin_amdgcn_raw_buffer_load_b128(rs##Q, off2, (R) * sst, 0); }\n";
+        if (fused)
+            // framing (broadcast.rs:174-189) folded into the loads: logical byte b
+            // of the framed value is payload byte b - 4.  The buffer resource
+            // covers the whole dwords of the payload (P & ~3 bytes; range checks
+            // are per dword), so everything past them reads 0; the 0-3 bytes of a
+            // partial last dword are added, with their parity, by frame_fixup.
+            o << "  const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(\n"
+                 "      (void *)(payloads + inst * payload_stride), (short)0, (int)(P & ~3u), 0x00020000);\n"
+                 "  const bool edge = !__all(off + 1024u + 16u <= S);\n"
+                 // dword-aligned start: the 16 framed bytes of a piece are bytes
+                 // bs..bs+15 of 20 loaded bytes, bs = (j*S - 4) & 3 (uniform per row)
+                 // (the address add is volatile asm: LLVM would otherwise hoist every
+                 // row's address out of the pass loop and keep k of them live)
+                 "#define HB_LDF2(QA, QA2, QB, QB2, j) { unsigned a_, b_; "
+                 "__asm__ volatile(\"v_add_u32 %0, %1, %2\" : \"=v\"(a_) : \"s\"((j) * S - 4u), \"v\"(off)); "
+                 "__asm__ volatile(\"v_add_u32 %0, %1, %2\" : \"=v\"(b_) : \"s\"((j) * S - 4u), \"v\"(off2)); "
+                 "a_ &= ~3u; b_ &= ~3u; "
+                 // a window starting inside the length prefix loads payload dwords 0..4
+                 "if ((j) < 4u && (j) * S + off < 4u) a_ = 0u; "
+                 "QA = __builtin_amdgcn_raw_buffer_load_b128(pr, a_, 0, 0); "
+                 "QA2 = __builtin_amdgcn_raw_buffer_load_b32(pr, a_ + 16u, 0, 0); "
+                 "QB = __builtin_amdgcn_raw_buffer_load_b128(pr, b_, 0, 0); "
+                 "QB2 = __builtin_amdgcn_raw_buffer_load_b32(pr, b_ + 16u, 0, 0); }\n";
+    }
+
+    void epilogue() { o << "#undef HB_LD\n" << (fused ? "#undef HB_LDF2\n" : ""); }
+
+    // load buffers for nbuf rows in flight
+    void buffers(int nbuf) {
+        if (fused)
+            o << "u32x4 q0[" << nbuf << "], q1[" << nbuf << "]; uint32_t q2[" << nbuf << "], q3[" << nbuf
+              << "];\n";
+        else
+            o << "u32x4 l[" << nbuf << "], h[" << nbuf << "];\n";
+    }
+
+    // request input `row` (its payload bytes when fused) into buffer b
+    void load(int row, int b) {
+        if (fused)
+            o << "      HB_LDF2(q0[" << b << "], q2[" << b << "], q1[" << b << "], q3[" << b << "], " << row
+              << "u)";
+        else
+            o << "      HB_LD(l[" << b << "], h[" << b << "], " << blk(row) << ", " << rin(row) << "u)";
+        // the empty asm keeps the scheduler from hoisting every row's load to
+        // the top of the straight-line code (hundreds of live VGPRs)
+        o << " __asm__ volatile(\"\" ::: \"memory\");\n";
+    }
+
+    // open a block with x[8] = the lane's 32 bytes of input `row` from buffer
+    // b; uf_put: a fused-unframe decoder writes the row's payload bytes here
+    void words(int row, int b, bool uf_put) {
+        if (fused) {
+            o << "      { uint32_t x[8];\n"
+                 "        hb_window2(q0[" << b << "], q2[" << b << "], q1[" << b << "], q3[" << b << "], ("
+              << row << "u * S - 4u) & 3u, x);\n";
+            // windows touching the BE32 payload length (broadcast.rs:175-177);
+            // j * S < 4 needs j < 4 since S >= 1
+            if (row < 4)
+                o << "        if (" << row << "u * S < 4u) { if (off == 0u) hb_frame_head2(q0[" << b
+                  << "], P, " << row << "u * S, x); }\n";
+            // positions >= S of this row belong to the next shard: zero
+            o << "        if (edge) {\n"
+                 "          _Pragma(\"unroll\") for (int i_ = 0; i_ < 8; ++i_) {\n"
+                 "            const int lim_ = (int)S - (int)(i_ < 4 ? off + 4 * i_ : off2 + 4 * (i_ - 4));\n"
+                 "            x[i_] = lim_ >= 4 ? x[i_] : (lim_ <= 0 ? 0u : x[i_] & (0xFFFFFFFFu >> (8 * (4 - lim_))));\n"
+                 "          }\n        }\n";
+            return;
+        }
+        o << "      { const u32x4 hh = full ? h[" << b << "] : (u32x4)(0u);\n"
+          << "        uint32_t x[8] = {l[" << b << "][0], l[" << b << "][1], l[" << b << "][2], l[" << b
+          << "][3], hh[0], hh[1], hh[2], hh[3]};\n";
+        if (uf_put && p.uf_k > 0 && p.uf_inputs && row < p.uf_k)
+            o << "        if (ufp && active) { hb_uf_put(ufp, S, " << row
+              << "u, off, x[0], x[1], x[2], x[3]); if (full) hb_uf_put(ufp, S, " << row
+              << "u, off2, x[4], x[5], x[6], x[7]); }\n";
+    }
+
+    // store x[8] as the framed data row `row`
+    void store_data_row(int row) {
+        o << "        if (active) {\n"
+             "          __builtin_amdgcn_raw_buffer_store_b128((u32x4){x[0], x[1], x[2], x[3]}, rs"
+          << blk(row) << ", off, " << rin(row) << "u * sst, HB_ST_AUX);\n"
+             "          if (full) __builtin_amdgcn_raw_buffer_store_b128((u32x4){x[4], x[5], x[6], x[7]}, "
+             "rs" << blk(row) << ", off2, " << rin(row) << "u * sst, HB_ST_AUX);\n        }\n";
+    }
+
+    // transpose and store the accumulators a[0..rows) as output rows t0.., with
+    // the payload bytes of rebuilt data rows in a fused-unframe decoder
+    void store_outputs(int t0, int rows) {
         o << "      if (active) {\n";
         for (int t = 0; t < rows; ++t) {
             const int row = p.out_rows[t0 + t];
@@ -491,43 +433,94 @@ std::string gen_xor_kernel(const XorProgram &p, bool fused) {
                   << "[1], " << at << "[2], " << at << "[3]); if (full) hb_uf_put(ufp, S, " << row
                   << "u, off2, " << at << "[4], " << at << "[5], " << at << "[6], " << at << "[7]); }\n";
         }
-        o << "      }\n      break; }\n";
+        o << "      }\n";
     }
-    o << "    }\n  }\n}\n#undef HB_LD\n" << (fused ? "#undef HB_LDF\n#undef HB_LDF2\n" : "");
+
+    // the XOR network of input jj into the accumulators of rows t0..t0+rows-1:
+    // nibble-subset for short passes, else pairwise.  The accumulators are
+    // pinned after every input: without this the reassociation pass flattens
+    // each accumulator's whole XOR chain over all inputs and keeps every
+    // input's planes live at once
+    void network(int t0, int rows, int jj) {
+        if (rt <= 8)
+            gen_nibble_network(o, cv, t0, rows, (size_t)jj);
+        else
+            gen_pair_network(o, cv, t0, rows, (size_t)jj);
+        o << "        for (int t_ = 0; t_ < " << rows << "; ++t_) for (int q_ = 0; q_ < 8; ++q_) "
+             "__asm__ volatile(\"\" : \"+v\"(a[t_][q_]));\n";
+    }
+};
+
+// Streaming form: a switch over the passes; every wave loads, frames and
+// transposes every input itself, depth rows ahead in register buffers.
+std::string gen_xor_kernel(const XorProgram &p, bool fused) {
+    Gen g(p, fused);
+    std::ostringstream &o = g.o;
+    const int nin = g.nin, npass = g.npass;
+    const int depth = fused ? kFusedDepth : p.depth;
+    const int nbuf = depth + 1;
+    g.gen_prologue("");
+
+    // wave w runs passes w, w + nw, ... of the same byte positions
+    o << "  for (int p = __builtin_amdgcn_readfirstlane(wave); p < " << npass
+      << "; p += nw) {\n    switch (p) {\n";
+    for (int ps = 0; ps < npass; ++ps) {
+        const int t0 = g.pass_lo(ps);
+        const int rows = g.pass_lo(ps + 1) - t0;
+        // a distinct barrier opens every case, so no common prefix (the first
+        // rows' loads) is hoisted above the switch and kept live across it
+        o << "    case " << ps << ": {\n      __asm__ volatile(\"; pass " << ps
+          << "\" ::: \"memory\");\n      uint32_t a[" << rows << "][8] = {};\n";
+        if (fused)
+            // S through an opaque SGPR copy per pass: otherwise every pass's row
+            // offsets (j * S - 4 and its byte shift) are loop-invariant, get
+            // hoisted above the pass loop and spill (41 SGPRs in the cfg3 encoder)
+            o << "      unsigned S_; __asm__ volatile(\"s_mov_b32 %0, %1\" : \"=s\"(S_) : \"s\"(S));\n"
+                 "      const unsigned S = S_;\n";
+        o << "      ";
+        g.buffers(nbuf);
+        // inputs 0..depth-1 in flight before the first product; input jj + depth
+        // is requested while input jj is consumed (depth rows of HBM latency hidden)
+        for (int jj = 0; jj < depth && jj < nin; ++jj) g.load(p.in_rows[jj], jj % nbuf);
+        for (int jj = 0; jj < nin; ++jj) {
+            const int row = p.in_rows[jj];
+            if (jj + depth < nin) g.load(p.in_rows[jj + depth], (jj + depth) % nbuf);
+            g.words(row, jj % nbuf, ps == 0);
+            // the data-row stores spread over the passes, pass jj % npass row jj
+            // (a store ahead of a load holds that load's vmcnt wait, and pass 0
+            // storing all 22 rows at cfg3 made it the workgroup's slowest wave)
+            if (g.writes_data_rows() && jj % npass == ps) g.store_data_row(row);
+            o << "        hb_tr(x);\n";
+            g.network(t0, rows, jj);
+            o << "      }\n";
+        }
+        g.store_outputs(t0, rows);
+        o << "      break; }\n";
+    }
+    o << "    }\n  }\n}\n";
+    g.epilogue();
     return o.str();
 }
 
-// LDS-staged form (p.lds): every input row of a stage is loaded, framed and
-// transposed ONCE per workgroup -- by wave jj % nw -- and its 8 bit planes go
-// to LDS ([jj][half][lane] u32x4: conflict-free 16-byte lane slots); after one
-// barrier every wave runs its pass over all inputs of the stage from LDS.  In
-// the streaming form each of the npass waves loads and transposes every input
-// itself (the transposes are ~25 % of a pass's VALU at cfg3) and keeps
+// LDS-staged form (xor_lds_form): every input row of a stage is loaded, framed
+// and transposed ONCE per workgroup -- by wave jj % nw -- and its 8 bit planes
+// go to LDS ([jj][half][lane] u32x4: conflict-free 16-byte lane slots); after
+// one barrier every wave runs its pass over all inputs of the stage from LDS.
+// In the streaming form each of the npass waves loads and transposes every
+// input itself (the transposes are ~25 % of a pass's VALU at cfg3) and keeps
 // depth + 1 rows of load buffers live beside its accumulators (231 VGPRs, 2
 // waves/SIMD); here a pass holds only its accumulators, 8 planes and the
-// network's temporaries.  Stages of <= 24 inputs (48 KB of LDS) bound the
-// LDS per workgroup; a barrier separates stages (the next stage's planes
-// overwrite the buffer).
+// network's temporaries.  Stages of kLdsStage inputs bound the LDS per
+// workgroup; a barrier separates stages (the next stage's planes overwrite
+// the buffer).
 std::string gen_xor_kernel_lds(const XorProgram &p, bool fused) {
-    const int nin = (int)p.in_rows.size();
-    const int nout = (int)p.out_rows.size();
-    const int npass = (nout + p.rt - 1) / p.rt;
-    auto pass_lo = [&](int ps) { return ps * (nout / npass) + std::min(ps, nout % npass); };
-    const int rt = (nout + npass - 1) / npass;
-    const int nw = xor_waves(npass);
-    const int rb = p.rb;
-    const CoefView cv{p.coefs.data(), (size_t)nin};
-    auto blk = [&](int row) { return row / rb; };
-    auto rin = [&](int row) { return row % rb; };
-    std::set<int> blocks;
-    for (int r : p.in_rows) blocks.insert(blk(r));
-    for (int r : p.out_rows) blocks.insert(blk(r));
-    const char *d2 = p.split ? "1024u" : "16u";
-    const int ss = std::min(nin, p.lds_stage > 0 ? p.lds_stage : 24);
+    Gen g(p, fused);
+    std::ostringstream &o = g.o;
+    const int nin = g.nin;
+    const int nw = xor_waves(g.npass);
+    const int ss = std::min(nin, kLdsStage);
     const int nstage = (nin + ss - 1) / ss;
-    std::ostringstream o;
-    gen_prologue(o, p, fused, npass, blocks, d2,
-                 "  __shared__ u32x4 hb_pl[" + std::to_string(ss) + "][2][64];\n");
+    g.gen_prologue("  __shared__ u32x4 hb_pl[" + std::to_string(ss) + "][2][64];\n");
     if (fused)
         // S through an opaque SGPR copy: otherwise the row offsets j * S - 4
         // of every input are hoisted and kept live
@@ -538,9 +531,9 @@ std::string gen_xor_kernel_lds(const XorProgram &p, bool fused) {
     // one case per wave; a wave runs pass w_ (npass <= 8 = nw here) and
     // loads the inputs jj of every stage with (jj - stage_lo) % nw == w_
     for (int w = 0; w < nw; ++w) {
-        const bool has_pass = w < npass;
-        const int t0 = has_pass ? pass_lo(w) : 0;
-        const int rows = has_pass ? pass_lo(w + 1) - t0 : 0;
+        const bool has_pass = w < g.npass;
+        const int t0 = has_pass ? g.pass_lo(w) : 0;
+        const int rows = has_pass ? g.pass_lo(w + 1) - t0 : 0;
         o << "  case " << w << ": {\n    __asm__ volatile(\"; wave " << w << "\" ::: \"memory\");\n";
         if (fused) o << "    const unsigned S = Sx;\n";
         if (rows) o << "    uint32_t a[" << rows << "][8] = {};\n";
@@ -551,104 +544,41 @@ std::string gen_xor_kernel_lds(const XorProgram &p, bool fused) {
                 if ((jj - lo) % nw == w) mine.push_back(jj);
             // phase 1: load (all of this wave's rows of the stage at once when
             // no accumulators are live yet, else two ahead), frame, transpose
-            const int depth = (st == 0) ? (int)mine.size() : std::min<int>(2, (int)mine.size());
+            const int n = (int)mine.size();
+            const int depth = (st == 0) ? n : std::min(2, n);
             const int nbuf = std::max(1, depth + (st == 0 ? 0 : 1));
-            if (!mine.empty()) {
-                if (fused)
-                    o << "    { u32x4 q0[" << nbuf << "], q1[" << nbuf << "]; uint32_t q2[" << nbuf << "]"
-                      << (p.split ? ", q3[" + std::to_string(nbuf) + "]" : std::string()) << ";\n";
-                else
-                    o << "    { u32x4 l[" << nbuf << "], h[" << nbuf << "];\n";
+            if (n) {
+                o << "    { ";
+                g.buffers(nbuf);
             }
-            auto load = [&](size_t m) {
-                const int b = (int)(m % nbuf);
+            for (int m = 0; m < depth; ++m) g.load(p.in_rows[mine[m]], m % nbuf);
+            for (int m = 0; m < n; ++m) {
                 const int row = p.in_rows[mine[m]];
-                if (fused && p.split)
-                    o << "      HB_LDF2(q0[" << b << "], q2[" << b << "], q1[" << b << "], q3[" << b << "], " << row << "u)";
-                else if (fused)
-                    o << "      HB_LDF(q0[" << b << "], q1[" << b << "], q2[" << b << "], " << row << "u)";
-                else
-                    o << "      HB_LD(l[" << b << "], h[" << b << "], " << blk(row) << ", " << rin(row) << "u)";
-                o << " __asm__ volatile(\"\" ::: \"memory\");\n";
-            };
-            for (int m = 0; m < depth; ++m) load((size_t)m);
-            for (size_t m = 0; m < mine.size(); ++m) {
-                const int jj = mine[m];
-                const int row = p.in_rows[jj];
-                const std::string c = std::to_string(m % nbuf);
-                if (m + depth < mine.size()) load(m + depth);
-                if (fused) {
-                    o << "      { uint32_t x[8];\n";
-                    if (p.split)
-                        o << "        hb_window2(q0[" << c << "], q2[" << c << "], q1[" << c << "], q3[" << c
-                          << "], (" << row << "u * S - 4u) & 3u, x);\n";
-                    else
-                        o << "        hb_window(q0[" << c << "], q1[" << c << "], q2[" << c << "], (" << row
-                          << "u * S - 4u) & 3u, x);\n";
-                    if (row < 4)
-                        o << "        if (" << row << "u * S < 4u) { if (off == 0u) "
-                          << (p.split ? "hb_frame_head2(q0[" + c + "], " : "hb_frame_head(q0[" + c + "], q1[" + c + "], ")
-                          << "P, " << row << "u * S, x); }\n";
-                    o << "        if (edge) {\n"
-                         "          _Pragma(\"unroll\") for (int i_ = 0; i_ < 8; ++i_) {\n"
-                         "            const int lim_ = (int)S - (int)(i_ < 4 ? off + 4 * i_ : off2 + 4 * (i_ - 4));\n"
-                         "            x[i_] = lim_ >= 4 ? x[i_] : (lim_ <= 0 ? 0u : x[i_] & (0xFFFFFFFFu >> (8 * (4 - lim_))));\n"
-                         "          }\n        }\n";
-                    // the first parity group writes the framed data rows
-                    if (p.out_rows.front() == nin)
-                        o << "        if (active) {\n"
-                             "          __builtin_amdgcn_raw_buffer_store_b128((u32x4){x[0], x[1], x[2], x[3]}, rs"
-                          << blk(row) << ", off, " << rin(row) << "u * sst, HB_ST_AUX);\n"
-                             "          if (full) __builtin_amdgcn_raw_buffer_store_b128((u32x4){x[4], x[5], x[6], x[7]}, "
-                             "rs" << blk(row) << ", off2, " << rin(row) << "u * sst, HB_ST_AUX);\n        }\n";
-                } else {
-                    o << "      { const u32x4 hh = full ? h[" << c << "] : (u32x4)(0u);\n"
-                      << "        uint32_t x[8] = {l[" << c << "][0], l[" << c << "][1], l[" << c << "][2], l[" << c
-                      << "][3], hh[0], hh[1], hh[2], hh[3]};\n";
-                    if (p.uf_k > 0 && p.uf_inputs && row < p.uf_k)
-                        o << "        if (ufp && active) { hb_uf_put(ufp, S, " << row
-                          << "u, off, x[0], x[1], x[2], x[3]); if (full) hb_uf_put(ufp, S, " << row
-                          << "u, off2, x[4], x[5], x[6], x[7]); }\n";
-                }
+                if (m + depth < n) g.load(p.in_rows[mine[m + depth]], (m + depth) % nbuf);
+                g.words(row, m % nbuf, true);
+                if (g.writes_data_rows()) g.store_data_row(row);
                 o << "        hb_tr(x);\n"
-                     "        hb_pl[" << (jj - lo) << "][0][lane] = (u32x4){x[0], x[1], x[2], x[3]};\n"
-                     "        hb_pl[" << (jj - lo) << "][1][lane] = (u32x4){x[4], x[5], x[6], x[7]};\n"
+                     "        hb_pl[" << (mine[m] - lo) << "][0][lane] = (u32x4){x[0], x[1], x[2], x[3]};\n"
+                     "        hb_pl[" << (mine[m] - lo) << "][1][lane] = (u32x4){x[4], x[5], x[6], x[7]};\n"
                      "      }\n";
             }
-            if (!mine.empty()) o << "    }\n";
+            if (n) o << "    }\n";
             o << "    __syncthreads();\n";
             // phase 2: this wave's pass over the stage's inputs
             for (int jj = lo; jj < hi && rows; ++jj) {
                 o << "    { const u32x4 pa_ = hb_pl[" << (jj - lo) << "][0][lane], pb_ = hb_pl[" << (jj - lo)
                   << "][1][lane];\n"
                      "      const uint32_t x[8] = {pa_[0], pa_[1], pa_[2], pa_[3], pb_[0], pb_[1], pb_[2], pb_[3]};\n";
-                gen_network(o, cv, t0, rows, (size_t)jj, rt, p.net);
-                o << "      for (int t_ = 0; t_ < " << rows << "; ++t_) for (int q_ = 0; q_ < 8; ++q_) "
-                     "__asm__ volatile(\"\" : \"+v\"(a[t_][q_]));\n"
-                     "      __asm__ volatile(\"\" ::: \"memory\");\n    }\n";
+                g.network(t0, rows, jj);
+                o << "      __asm__ volatile(\"\" ::: \"memory\");\n    }\n";
             }
             if (st + 1 < nstage) o << "    __syncthreads();\n";
         }
-        if (rows) {
-            o << "    if (active) {\n";
-            for (int t = 0; t < rows; ++t) {
-                const int row = p.out_rows[t0 + t];
-                const std::string at = "a[" + std::to_string(t) + "]";
-                o << "      { hb_tr(" << at << "); const unsigned so_ = " << rin(row) << "u * sst;\n"
-                  << "        __builtin_amdgcn_raw_buffer_store_b128((u32x4){" << at << "[0], " << at << "[1], "
-                  << at << "[2], " << at << "[3]}, rs" << blk(row) << ", off, so_, HB_ST_AUX);\n"
-                  << "        if (full) __builtin_amdgcn_raw_buffer_store_b128((u32x4){" << at << "[4], " << at
-                  << "[5], " << at << "[6], " << at << "[7]}, rs" << blk(row) << ", off2, so_, HB_ST_AUX); }\n";
-                if (p.uf_k > 0 && row < p.uf_k)
-                    o << "      if (ufp) { hb_uf_put(ufp, S, " << row << "u, off, " << at << "[0], " << at
-                      << "[1], " << at << "[2], " << at << "[3]); if (full) hb_uf_put(ufp, S, " << row
-                      << "u, off2, " << at << "[4], " << at << "[5], " << at << "[6], " << at << "[7]); }\n";
-            }
-            o << "    }\n";
-        }
+        if (rows) g.store_outputs(t0, rows);
         o << "    break; }\n";
     }
-    o << "  }\n}\n#undef HB_LD\n" << (fused ? "#undef HB_LDF\n#undef HB_LDF2\n" : "");
+    o << "  }\n}\n";
+    g.epilogue();
     return o.str();
 }
 
@@ -656,36 +586,32 @@ std::string gen_xor_kernel_lds(const XorProgram &p, bool fused) {
 
 int xor_waves(int npass) { return std::max(1, std::min(8, npass)); }
 
-std::string encode_kernel_name(size_t k, size_t m, int rt, int depth, int r_lo, int r_hi, int rb,
-                               int sync, int fdepth, bool spread, bool split) {
+bool xor_lds_form(const XorProgram &p) {
+    const int npass = (int)((p.out_rows.size() + p.rt - 1) / p.rt);
+    return p.lds && npass >= 2 && npass <= 8;
+}
+
+std::string encode_kernel_name(size_t k, size_t m, int rt, int depth, int r_lo, int r_hi, int rb) {
     char b[128];
     snprintf(b, sizeof b, "hbrbc_enc_k%zu_m%zu_rt%d_d%d_r%d_%d", k, m, rt, depth, r_lo, r_hi);
     std::string s = b;
     if (rb < 256) s += "_b" + std::to_string(rb);
-    if (sync > 0) s += "_s" + std::to_string(sync);
-    if (fdepth != 2) s += "_f" + std::to_string(fdepth);
-    if (!spread) s += "_w0";
-    if (!split) s += "_c";
     return s;
 }
 
 std::string decode_kernel_name(size_t n, uint64_t hash, int rt, int depth, int r_lo, int r_hi,
-                               int rb, int sync, bool split) {
+                               int rb) {
     char b[128];
     snprintf(b, sizeof b, "hbrbc_dec_n%zu_%016llx_rt%d_d%d_r%d_%d", n, (unsigned long long)hash,
              rt, depth, r_lo, r_hi);
     std::string s = b;
     if (rb < 256) s += "_b" + std::to_string(rb);
-    if (sync > 0) s += "_s" + std::to_string(sync);
-    if (!split) s += "_c";
     return s;
 }
 
 std::vector<std::pair<int, int>> xor_groups(size_t nin, size_t nout, int rt) {
     // a group = one hiprtc program; bigger ones compile superlinearly slowly
-    // (HBRBC_JIT_GROUP: coefficients per program, A/B)
-    const char *ge = getenv("HBRBC_JIT_GROUP");
-    const size_t kMaxCoefs = ge ? std::max<size_t>(256, (size_t)atol(ge)) : (size_t)4096;
+    const size_t kMaxCoefs = 4096;
     std::vector<std::pair<int, int>> g;
     size_t per = nout;
     if (nin * nout > kMaxCoefs) per = std::max<size_t>((size_t)rt, kMaxCoefs / nin / rt * rt);
@@ -698,11 +624,9 @@ std::vector<std::pair<int, int>> xor_groups(size_t nin, size_t nout, int rt) {
 }
 
 std::string gen_xor_source(const XorProgram &p) {
-    const int npass = (int)((p.out_rows.size() + p.rt - 1) / p.rt);
-    const bool lds = p.lds && npass >= 2 && npass <= 8;
-    auto gen = [&](bool fused) { return lds ? gen_xor_kernel_lds(p, fused) : gen_xor_kernel(p, fused); };
-    std::string s = std::string(kPrelude) + gen(false);
-    if (p.fused) s += gen(true);
+    const auto gen = xor_lds_form(p) ? gen_xor_kernel_lds : gen_xor_kernel;
+    std::string s = std::string(kPrelude) + gen(p, false);
+    if (p.fused) s += gen(p, true);
     return s;
 }
 
@@ -713,11 +637,8 @@ int compile_source(const std::string &src, std::vector<char> &code, std::string 
         log = "hiprtcCreateProgram failed";
         return -1;
     }
-    // HBRBC_ST_AUX (A/B): cache-policy bits of the row stores
-    const char *aux = getenv("HBRBC_ST_AUX");
-    const std::string aux_def = std::string("-DHB_ST_AUX=") + (aux ? aux : "2");
-    const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", aux_def.c_str()};
-    const hiprtcResult r = hiprtcCompileProgram(prog, 4, opts);
+    const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17"};
+    const hiprtcResult r = hiprtcCompileProgram(prog, 3, opts);
     size_t lsz = 0;
     hiprtcGetProgramLogSize(prog, &lsz);
     if (lsz > 1) {

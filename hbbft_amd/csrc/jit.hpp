@@ -24,16 +24,9 @@ struct XorProgram {
     std::string name;
     std::vector<int> in_rows, out_rows;
     std::vector<uint8_t> coefs;  // [out_rows.size()][in_rows.size()]
+    // output rows per pass (at most; passes are balanced), input rows in
+    // flight of the streaming form, rows per block
     int rt = 2, depth = 4, rb = 256;
-    // > 0: a raw s_barrier after every `sync` input rows (every wave runs one
-    // pass, so the waves of a workgroup stream the input rows in lockstep)
-    int sync = 0;
-    // prefetch depth of the frame+encode twin (its rows are 36 loaded bytes)
-    int fdepth = 2;
-    // frame+encode twin: the data-row stores spread over the passes (else pass 0)
-    bool spread = true;
-    // lane byte positions: two 16-byte pieces 1 KB apart (else 32 consecutive)
-    bool split = true;
     uint64_t guard = 0;
     bool fused = false;
     // fused unframe (decoders): payload bytes of the data rows (< uf_k) this
@@ -41,21 +34,19 @@ struct XorProgram {
     // of a pattern writes them); 0 = none
     int uf_k = 0;
     bool uf_inputs = false;
-    // LDS-staged form (gen_xor_kernel_lds): each input transposed once per
-    // workgroup, planes shared through LDS; stages of lds_stage inputs
+    // LDS-staged form wanted (taken if xor_lds_form): each input transposed
+    // once per workgroup, planes shared through LDS
     bool lds = false;
-    int lds_stage = 0;
     // chunk order: a workgroup's chunk chosen so that each XCD walks
-    // consecutive chunks (jit.hip gen_prologue)
+    // consecutive chunks (jit.hip Gen::gen_prologue)
     bool xcd = false;
-    // network: 0 auto (nibble-subset for passes <= 8 rows, else pairwise),
-    // 1 pairwise, 2 nibble-subset
-    int net = 0;
     // > 0: amdgpu_waves_per_eu (the register budget the compiler targets)
     int wpe = 0;
 };
 
-// Kernel argument list shared by every generated kernel (hipModuleLaunchKernel).
+// Kernel argument list shared by every generated kernel, in the order of the
+// generated signature (jit.hip Gen::gen_prologue) and of the args[] array of the
+// launcher (api.hip launch_xor_group).
 struct XorArgs {
     uint8_t *base;
     unsigned long inst_stride, shard_stride, block_stride;
@@ -66,7 +57,6 @@ struct XorArgs {
     const int *pat;
     const unsigned long *slot_hash;
     int hash_slots;
-    int p_only;
     // fused unframe: payload slab (nullptr = off), its stride, reconstruct status
     uint8_t *uf_payload;
     unsigned long uf_stride;
@@ -75,6 +65,9 @@ struct XorArgs {
 
 // Waves per workgroup of a program with npass passes (one per pass, <= 8).
 int xor_waves(int npass);
+// Whether the program takes the LDS-staged form: asked for (p.lds) and 2..8
+// passes, one wave each; every other program streams.
+bool xor_lds_form(const XorProgram &p);
 std::string gen_xor_source(const XorProgram &p);
 // hiprtc-compile a generated source for gfx950 (no device needed).  0 on success.
 int compile_source(const std::string &src, std::vector<char> &code, std::string &log);
@@ -82,11 +75,9 @@ int compile_source(const std::string &src, std::vector<char> &code, std::string 
 // Names: encoder group (k, m, rt, depth, parity rows [r_lo, r_hi), rows per
 // block) and decoder group (n, pattern hash, rt, depth, output rows [r_lo,
 // r_hi) of the pattern's missing-row list, rows per block).
-std::string encode_kernel_name(size_t k, size_t m, int rt, int depth, int r_lo, int r_hi, int rb,
-                               int sync = 0, int fdepth = 2, bool spread = true,
-                               bool split = false);
+std::string encode_kernel_name(size_t k, size_t m, int rt, int depth, int r_lo, int r_hi, int rb);
 std::string decode_kernel_name(size_t n, uint64_t hash, int rt, int depth, int r_lo, int r_hi,
-                               int rb, int sync = 0, bool split = true);
+                               int rb);
 // Output-row groups [lo, hi), one hiprtc program each (large matrices are
 // split so each program stays near 4096 coefficients).
 std::vector<std::pair<int, int>> xor_groups(size_t nin, size_t nout, int rt);

@@ -172,19 +172,12 @@ __global__ __launch_bounds__(kBlock) void frame_fixup_kernel(
 }
 
 // 16-byte store of a streamed output (rebuilt rows, payloads), non-temporal:
-// unframe 1.82 -> 1.62 ms, reconstruct 3.10 -> 3.05 ms at cfg3 (HB_NT=0
-// builds the plain store for A/B).
-#ifndef HB_NT
-#define HB_NT 1
-#endif
+// unframe 1.82 -> 1.62 ms, reconstruct 3.10 -> 3.05 ms at cfg3 against the
+// plain store.
 typedef unsigned int hb_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store16_stream(void *p, uint32_t a, uint32_t b, uint32_t c,
                                                uint32_t d) {
-#if HB_NT
     __builtin_nontemporal_store((hb_u32x4){a, b, c, d}, reinterpret_cast<hb_u32x4 *>(p));
-#else
-    *reinterpret_cast<uint4 *>(p) = make_uint4(a, b, c, d);
-#endif
 }
 
 // ------------------------------------------------------- GF bit-sliced ----
@@ -241,12 +234,7 @@ template <int RT, int MODE>
 // its passes one after another re-read every input per pass: 3x the HBM/MALL
 // traffic at m = 42).  Instance i uses the coefficients and row lists of
 // slot pat[i] (the decode-matrix cache) or of slot i / the shared slot 0.
-#ifdef HB_GF_WPE   // A/B: waves per SIMD the register budget is cut to
-#define HB_GF_ATTR __attribute__((amdgpu_waves_per_eu(HB_GF_WPE)))
-#else
-#define HB_GF_ATTR
-#endif
-__global__ __launch_bounds__(256) HB_GF_ATTR void gf_bitslice_kernel(
+__global__ __launch_bounds__(256) void gf_bitslice_kernel(
     uint8_t *__restrict__ base, size_t inst_stride, RowMap rows, uint32_t row_bytes,
     const uint8_t *__restrict__ coefs, size_t coef_slot_stride,
     const uint32_t *__restrict__ in_idx, size_t in_idx_stride,
@@ -590,10 +578,7 @@ __global__ __launch_bounds__(256) HB_GF_ATTR void gf_bitslice_kernel(
 // (slens != nullptr: ragged batch, instance i's shards are slens[i] bytes.)
 // Sponge kernels: at most 128 VGPRs (4 waves/SIMD, the residency the
 // Keccak ceiling was measured at); V16 = few-sponge grids (16-byte loads).
-#ifndef HB_SPONGE_WPE
-#define HB_SPONGE_WPE 4   // waves/SIMD of the 8-byte-load sponge kernels (A/B: -DHB_SPONGE_WPE)
-#endif
-#define HB_SPONGE_ATTR __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(V16 ? 1 : HB_SPONGE_WPE)))
+#define HB_SPONGE_ATTR __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(V16 ? 1 : 4)))
 template <bool V16>
 __global__ HB_SPONGE_ATTR void leaf_hash_kernel(
     const uint8_t *__restrict__ shards, uint32_t S, RowMap rows, size_t inst_stride,

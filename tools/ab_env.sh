@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of environment knobs over bench configurations, one bench run each:
-#   VAR=HBRBC_JIT_SYNC VALUES="0 2 4" CONFIGS="cfg5 cfg3" bash tools/ab_env.sh
-#   SETS="HBRBC_RT_SPEC=14 HBRBC_RT_SPEC=11,HBRBC_JIT_FDEPTH=4" bash tools/ab_env.sh
+#   VAR=HBRBC_JIT_XCD VALUES="0 1" CONFIGS="cfg5 cfg3" bash tools/ab_env.sh
+#   SETS="HBRBC_JIT_XCD=0 HBRBC_JIT_XCD=1,HBRBC_UNFRAME_FUSED=0" bash tools/ab_env.sh
 # (SETS: each word one comma-separated list of VAR=value assignments)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/ab

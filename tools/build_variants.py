@@ -4,8 +4,8 @@ objects under hbbft_amd/jit/) with environment knobs, one fresh process per
 code object so no knob leaks from one build into the next.
 
 usage: python tools/build_variants.py 'ENV=V[,ENV=V...]' [...] --n 64 [--dec] [-j 8]
-  each positional argument is one variant, e.g. HBRBC_RT_SPEC=8 or
-  HBRBC_RT_SPEC=14,HBRBC_JIT_FDEPTH=4; --n picks the validator count (f =
+  each positional argument is one variant, e.g. HBRBC_JIT_XCD=0 or
+  HBRBC_JIT_XCD=1,HBRBC_JIT_DIR=/tmp/xcd1; --n picks the validator count (f =
   (n-1)//3); --dec also builds the decoders of the bench's fixed patterns for n,
   --uf their fused-unframe variants.
 """

@@ -2,7 +2,7 @@
 """Frame + encode alone (hbrbc_frame_encode_batch, the specialised encoder of
 the bench's context) over a cfg3-sized batch already in HBM: ms per launch
 (HIP events, median of --reps), for A/B of encoder code-object variants
-(HBRBC_RT_SPEC, HBRBC_JIT_WPE, ... as in tools/build_variants.py).
+(HBRBC_JIT_XCD=0/1, built with tools/build_variants.py).
 
 usage: python tools/enc_bench.py [--n 64] [--count 16384] [--plen 262144]
 """
