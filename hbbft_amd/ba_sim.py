@@ -31,13 +31,12 @@ node's decision, decision epoch, fault log, the round count and the per-round
 record totals against the host restatement (hbbft_amd/binary_agreement.py
 driven by tests/ba_net.py RoundNet) on the same scenarios.
 """
-import ctypes
-
 import numpy as np
 import torch
 
-from . import _check, lib
+from . import rounds as shared
 from .binary_agreement import CoinTable
+from .rounds import I32, U32, USIZE
 
 NONE = 0xFF
 HONEST, SILENT, TWO_FACED, BAD_COIN, REPLAY, AHEAD, REPLAY_AHEAD = range(7)
@@ -51,19 +50,21 @@ FORMS = {"global": FORM_GLOBAL, "staged": FORM_STAGED, "staged_w3": FORM_STAGED_
 # hbrbc_ba_args.emitted[1]
 BAD_OUT, BAD_QUEUE, BAD_COINS, BAD_EPOCH, BAD_STACK = 1, 2, 4, 8, 16
 
-_P = ctypes.c_void_p
+# hbrbc_ba_args.emitted[1] of a round, in the order the read-back looks at them
+ROUND_FLAGS = (
+    (BAD_QUEUE, "agreement: a message for an epoch beyond the future-epoch ring of "
+                "{0.queue_epochs} slots (raise queue_epochs)"),
+    (BAD_COINS, "agreement: a node reached a coin slot past the {0.coins} of the tables"),
+    (BAD_OUT, "agreement: a node emitted more than {0.max_out} messages in a round"),
+    (shared.ANY, "agreement: internal limit hit (flags {1:#x})"))
 
-
-class BaArgs(ctypes.Structure):
-    """struct hbrbc_ba_args (include/hbrbc.h)."""
-    _fields_ = [("count", ctypes.c_size_t), ("n", ctypes.c_uint32), ("max_out", ctypes.c_uint32),
-                ("max_faults", ctypes.c_uint32), ("queue_epochs", ctypes.c_uint32),
-                ("coins", ctypes.c_uint32), ("round", ctypes.c_int32),
-                ("form", ctypes.c_uint32)] + [
-        (name, _P) for name in (
-            "input", "role", "flip", "ahead", "share_ok", "coin", "in_", "in_count", "out",
-            "out_count", "state", "decision", "decision_epoch", "faults", "fault_count",
-            "emitted", "active")]
+BaArgs = shared.args_struct(
+    "BaArgs", "hbrbc_ba_args",
+    [("count", USIZE), ("n", U32), ("max_out", U32), ("max_faults", U32), ("queue_epochs", U32),
+     ("coins", U32), ("round", I32), ("form", U32)],
+    ("input", "role", "flip", "ahead", "share_ok", "coin", "in_", "in_count", "out", "out_count",
+     "state", "decision", "decision_epoch", "faults", "fault_count", "emitted", "active"))
+BA_ROUND = shared.Entry("hbrbc_ba_round", BaArgs, sizes=("hbrbc_ba_state_bytes",))
 
 
 def ba_state_bytes_host(n, queue_epochs):
@@ -75,15 +76,9 @@ def ba_state_bytes_host(n, queue_epochs):
     return (4 * (2 + 9 * w) + 2 * n * queue_epochs + 15) & ~15
 
 
-def _bind():
-    L = lib()
-    if not getattr(L, "_ba_bound", False):
-        L.hbrbc_ba_state_bytes.restype = ctypes.c_size_t
-        L.hbrbc_ba_state_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t]
-        L.hbrbc_ba_round.restype = ctypes.c_int
-        L.hbrbc_ba_round.argtypes = [ctypes.POINTER(BaArgs), _P]
-        L._ba_bound = True
-    return L
+def state_bytes(n, queue_epochs):
+    """hbrbc_ba_state_bytes of the library."""
+    return BA_ROUND.bind().hbrbc_ba_state_bytes(n, queue_epochs)
 
 
 # ------------------------------------------------------------------ scenario --
@@ -169,7 +164,7 @@ class Scenario:
 
 
 # ------------------------------------------------------------- one rank -----
-class BaRank:
+class BaRank(shared.HasAgreement):
     """Every node of `count` instances.  `sc`: the scenario tensors
     (Scenario.tensors).  form: FORM_AUTO or one of FORMS (the launch form is
     an argument of every round, hbrbc_ba_args.form)."""
@@ -177,26 +172,15 @@ class BaRank:
     def __init__(self, n, count, coins, sc, device=0, max_out=24, max_faults=64, queue_epochs=4,
                  max_rounds=256, form=FORM_AUTO):
         self.n, self.count, self.coins = n, count, coins
-        self.W = (n + 31) // 32
-        self.rec = 1 + self.W
         self.max_out, self.max_faults, self.queue_epochs = max_out, max_faults, queue_epochs
         self.max_rounds, self.form = max_rounds, form
         dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.device = dev
         self.sc = sc
-        sb = _bind().hbrbc_ba_state_bytes(n, queue_epochs)
-        i32 = dict(dtype=torch.int32, device=dev)
-        self.state = torch.zeros((count, n, sb), dtype=torch.uint8, device=dev)
-        self.out = torch.zeros((count, n, max_out, self.rec), **i32)
-        self.out_count = torch.zeros((count, n), **i32)
-        self.inbox = torch.zeros((count, n, max_out, self.rec), **i32)
-        self.inbox_count = torch.zeros((count, n), **i32)
-        self.decision = torch.full((count, n), NONE, dtype=torch.uint8, device=dev)
-        self.decision_epoch = torch.zeros((count, n), dtype=torch.int16, device=dev)
-        self.faults = torch.zeros((count, n, max(1, max_faults)), dtype=torch.int16, device=dev)
-        self.fault_count = torch.zeros((count, n), **i32)
+        self.ag = shared.AgreementState(count, n, state_bytes(n, queue_epochs), max_out,
+                                        max_faults, dev)
         # per round: records emitted, flags (hbrbc_ba_args.emitted of round r)
-        self.hist = torch.zeros((max_rounds, 2), **i32)
+        self.hist = torch.zeros((max_rounds, 2), dtype=torch.int32, device=dev)
         self.records = 0   # records emitted over the last run (all rounds)
 
     @classmethod
@@ -207,19 +191,9 @@ class BaRank:
 
     def reset(self):
         """Fresh nodes (before round 0 of another run)."""
-        self.state.zero_()
+        self.ag.reset()
         self.hist.zero_()
-        self.out_count.zero_()
-        self.inbox_count.zero_()
-        self.decision.fill_(NONE)
-        self.decision_epoch.zero_()
-        self.fault_count.zero_()
         self.records = 0
-
-    def swap_local(self):
-        """This round's records become the next round's inbox."""
-        self.inbox, self.out = self.out, self.inbox
-        self.inbox_count, self.out_count = self.out_count, self.inbox_count
 
     def round(self, r, active=None, stream=None):
         """Handle round r's inbox (round 0: propose).  active: None, or a
@@ -227,21 +201,11 @@ class BaRank:
         kernel returns at once when it is 0."""
         if r >= self.max_rounds:
             raise RuntimeError("agreement: round %d past max_rounds %d" % (r, self.max_rounds))
-        s = self.sc
         a = BaArgs(count=self.count, n=self.n, max_out=self.max_out, max_faults=self.max_faults,
                    queue_epochs=self.queue_epochs, coins=self.coins, round=r, form=self.form)
-        for name in ("input", "role", "flip", "ahead", "share_ok", "coin"):
-            setattr(a, name, s[name].data_ptr())
-        a.in_, a.in_count = self.inbox.data_ptr(), self.inbox_count.data_ptr()
-        a.out, a.out_count = self.out.data_ptr(), self.out_count.data_ptr()
-        a.state = self.state.data_ptr()
-        a.decision, a.decision_epoch = self.decision.data_ptr(), self.decision_epoch.data_ptr()
-        a.faults, a.fault_count = self.faults.data_ptr(), self.fault_count.data_ptr()
-        a.emitted = self.hist[r].data_ptr()
-        a.active = None if active is None else active.data_ptr()
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _check(_bind().hbrbc_ba_round(ctypes.byref(a), ctypes.c_void_p(st.cuda_stream)))
+        self.ag.write(a)
+        shared.fill(a, self.sc, self.hist, r, active)
+        BA_ROUND.launch(a, self.device, stream)
 
     def emitted(self, r):
         """Device int32 scalar: records emitted in round r."""
@@ -254,72 +218,26 @@ class BaRank:
 
     def fault_logs(self):
         """{(inst, node): [(blamed node, FaultKind name)]}."""
-        fc = self.fault_count.cpu().numpy()
-        fl = self.faults.cpu().numpy().view(np.uint16)
-        out = {}
-        for i in range(self.count):
-            for node in range(self.n):
-                cnt = int(fc[i, node])
-                if cnt > self.max_faults:
-                    raise RuntimeError("fault log overflow at (%d, %d): %d records"
-                                       % (i, node, cnt))
-                out[(i, node)] = [(int(v) >> 8, FAULT_KINDS[int(v) & 0xFF])
-                                  for v in fl[i, node, :cnt]]
-        return out
+        return shared.fault_logs(self.fault_count, self.faults, self.max_faults, FAULT_KINDS)
 
 
 ROUND_BATCH = 8   # rounds enqueued per read-back
 
 
-def _check_flags(rank, fl):
-    if fl & BAD_QUEUE:
-        raise RuntimeError("agreement: a message for an epoch beyond the future-epoch ring of "
-                           "%d slots (raise queue_epochs)" % rank.queue_epochs)
-    if fl & BAD_COINS:
-        raise RuntimeError("agreement: a node reached a coin slot past the %d of the tables"
-                           % rank.coins)
-    if fl & BAD_OUT:
-        raise RuntimeError("agreement: a node emitted more than %d messages in a round"
-                           % rank.max_out)
-    if fl:
-        raise RuntimeError("agreement: internal limit hit (flags %#x)" % fl)
-
-
-def run_rounds(rank, stream=None):
-    """Drive the state machine until no node emits a message: batches of
-    ROUND_BATCH rounds are enqueued, round r with the device count of round
-    r - 1 as `active` (a quiescent network costs empty launches), and the
-    per-round counts and flags are read back once per batch.  (rbc_sim.
-    LocalRounds reads the flags of Broadcast; this is the same loop with the
-    flags of hbrbc_ba_args.emitted.)  Returns the number of rounds, in
-    rbc_sim's convention: the index of the first round without records + 1.
-    Every run starts from fresh nodes."""
-    ctx = torch.cuda.stream(stream) if stream is not None else _nullctx()
-    with ctx:
-        rank.reset()
-        r = 0
-        while True:
-            hi = min(rank.max_rounds, r + ROUND_BATCH)
-            for rr in range(r, hi):
-                rank.round(rr, active=None if rr == 0 else rank.emitted(rr - 1))
-                rank.swap_local()
-            h = rank.hist[r:hi].cpu().numpy()   # one read
-            for i in range(hi - r):
-                _check_flags(rank, int(h[i, 1]))
-                rank.records += int(h[i, 0])
-                if int(h[i, 0]) == 0:
-                    return r + i + 1
-            if hi >= rank.max_rounds:
-                raise RuntimeError("agreement did not quiesce in %d rounds" % rank.max_rounds)
-            r = hi
-
-
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
+def run_rounds(rank, stream=None, events=None):
+    """Drive the state machine until no node emits a message (rounds.Rounds):
+    batches of ROUND_BATCH rounds are enqueued, round r with the device count
+    of round r - 1 as `active` (a quiescent network costs empty launches), and
+    the per-round counts and flags are read back once per batch.  Returns the
+    number of rounds, in rbc_sim's convention: the index of the first round
+    without records + 1.  Every run starts from fresh nodes.  events: a list
+    that receives ("agreement", start, end) device events of every launch."""
+    def enqueue(r, phase):
+        phase("agreement", rank.round, r, None if r == 0 else rank.emitted(r - 1))
+        rank.ag.swap()
+    return shared.Rounds([shared.Protocol(ROUND_FLAGS, rank, rank, "records")], rank.max_rounds,
+                         ROUND_BATCH, "agreement", stream, events, reset=rank.reset,
+                         enqueue=enqueue, read=shared.hist_rows([rank])).launch().wait()
 
 
 class BaRun:
@@ -361,11 +279,6 @@ def simulate(scn, device=0, **kw):
 
 
 # ------------------------------------------------------------- data plane ---
-def _i32(values, dev):
-    a = np.asarray(values, dtype=np.int64).reshape(-1).astype(np.uint32)
-    return torch.from_numpy(a.view(np.int32).copy()).to(dev)
-
-
 def coin_plane(scn, hashes192, keys, device=0):
     """The data plane of the coin, on the existing G2 entries (hbbft_amd/
     threshold.py): hashes192[inst * coins + q] is the document point H of
@@ -381,6 +294,7 @@ def coin_plane(scn, hashes192, keys, device=0):
     combined signature passes the master key), sig_tab / sig_count / docs (the
     share table, node-major: threshold.share_row) for further combines."""
     from . import threshold as T
+    u32 = T._u32_tensor
     n, cnt = scn.n, scn.count
     C = len(hashes192)
     coins = C // cnt
@@ -402,10 +316,10 @@ def coin_plane(scn, hashes192, keys, device=0):
     other = [(c // coins) * coins + (c % coins + 1) % coins if coins > 1 else (c + 1) % C
              for c in range(C)]
     hprep = T.g2_prepare(T._g2_rows(hashes192, dev))
-    ok0 = T.sig_check_prepared(stab, total, pk_tab, n, _i32(nodes, dev), hprep, C, _i32(docs, dev))
-    swapped = s192[_i32([T.share_row(i, other[c], C) for i, c in zip(nodes, docs)], dev).long()]
+    ok0 = T.sig_check_prepared(stab, total, pk_tab, n, u32(nodes, dev), hprep, C, u32(docs, dev))
+    swapped = s192[u32([T.share_row(i, other[c], C) for i, c in zip(nodes, docs)], dev).long()]
     ok1 = T.sig_check_prepared(T.g2_points_prepare(swapped.contiguous()), total, pk_tab, n,
-                               _i32(nodes, dev), hprep, C, _i32(docs, dev))
+                               u32(nodes, dev), hprep, C, u32(docs, dev))
     # [node][doc] -> [inst][slot][node]
     share_ok = torch.stack([(o == T.CHECK_OK).to(torch.uint8).view(n, cnt, coins).permute(1, 2, 0)
                             for o in (ok0, ok1)], dim=2).contiguous()
@@ -421,14 +335,15 @@ def coin_parity(info, nodes, dev):
     document of a coin_plane: (parity uint8 [docs], verified uint8 [docs]: the
     signature passes the master public key)."""
     from . import threshold as T
+    u32 = T._u32_tensor
     C, k = info["docs"], len(nodes)
     rows = [T.share_row(i, c, C) for c in range(C) for i in nodes]
-    offs = _i32(np.arange(C + 1) * k, dev)
-    g192, _, par, st = T.sig_combine_prepared(info["sig_tab"], info["sig_count"], _i32(rows, dev),
-                                              _i32(list(nodes) * C, dev), offs)
+    offs = u32(np.arange(C + 1) * k, dev)
+    g192, _, par, st = T.sig_combine_prepared(info["sig_tab"], info["sig_count"], u32(rows, dev),
+                                              u32(list(nodes) * C, dev), offs)
     if st.cpu().numpy().any():
         raise ValueError("coin_plane: a combine failed")
     master = T.g1_prepare(T._g1_rows([info["keys"]["key_set"][0][0]], dev))
     ver = T.sig_check_prepared(T.g2_points_prepare(g192), C, master, 1,
-                               _i32([0] * C, dev), info["hprep"], C, _i32(list(range(C)), dev))
+                               u32([0] * C, dev), info["hprep"], C, u32(list(range(C)), dev))
     return par.to(torch.uint8), (ver == T.CHECK_OK).to(torch.uint8)

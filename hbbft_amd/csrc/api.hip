@@ -2082,20 +2082,35 @@ size_t hbrbc_ba_state_bytes(size_t n, size_t queue_epochs) {
     return ba_state_bytes(n, queue_epochs);
 }
 
+// The checks the round entries below share, in the order each of them makes
+// them: the validator count, the entry's own limits (`bad`: the message of the
+// first one that fails, or nullptr), the round, the entry's pointers
+// (`missing`), the device.
+static int round_checks(uint32_t n, const char *bad, int32_t round, bool missing) {
+    if (n == 0 || n > 255)
+        return fail(HBRBC_E_INVALID_ARG, "the state machine handles 1..255 validators");
+    if (bad) return fail(HBRBC_E_INVALID_ARG, "%s", bad);
+    if (round < 0) return fail(HBRBC_E_INVALID_ARG, "negative round");
+    if (missing) return fail(HBRBC_E_INVALID_ARG, "null argument");
+    return have_device();
+}
+
+// (hbrbc_ba_args, hbrbc_subset_args: the agreement's limits)
+static const char *bad_agreement_limits(uint32_t max_out, uint32_t queue_epochs, uint32_t coins) {
+    return max_out == 0 || queue_epochs == 0 || queue_epochs > 16 || coins == 0
+               ? "bad max_out / queue_epochs / coins" : nullptr;
+}
+
 int hbrbc_ba_round(const hbrbc_ba_args *a, void *stream) {
     if (!a) return fail(HBRBC_E_INVALID_ARG, "null argument");
     if (a->count == 0) return HBRBC_OK;
-    if (a->n == 0 || a->n > 255)
-        return fail(HBRBC_E_INVALID_ARG, "the state machine handles 1..255 validators");
-    if (a->max_out == 0 || a->queue_epochs == 0 || a->queue_epochs > 16 || a->coins == 0)
-        return fail(HBRBC_E_INVALID_ARG, "bad max_out / queue_epochs / coins");
-    if (a->form > HBRBC_BA_FORM_STAGED_W3) return fail(HBRBC_E_INVALID_ARG, "unknown launch form");
-    if (a->round < 0) return fail(HBRBC_E_INVALID_ARG, "negative round");
-    if (!a->input || !a->role || !a->flip || !a->ahead || !a->share_ok || !a->coin || !a->out ||
+    const char *bad = bad_agreement_limits(a->max_out, a->queue_epochs, a->coins);
+    if (!bad && a->form > HBRBC_BA_FORM_STAGED_W3) bad = "unknown launch form";
+    const bool missing =
+        !a->input || !a->role || !a->flip || !a->ahead || !a->share_ok || !a->coin || !a->out ||
         !a->out_count || !a->state || !a->decision || !a->decision_epoch || !a->fault_count ||
-        !a->emitted || (a->max_faults && !a->faults) || (a->round > 0 && (!a->in || !a->in_count)))
-        return fail(HBRBC_E_INVALID_ARG, "null argument");
-    if (int rc = have_device()) return rc;
+        !a->emitted || (a->max_faults && !a->faults) || (a->round > 0 && (!a->in || !a->in_count));
+    if (int rc = round_checks(a->n, bad, a->round, missing)) return rc;
     HB_HIP(launch_ba_round(*a, static_cast<hipStream_t>(stream)));
     return HBRBC_OK;
 }
@@ -2104,17 +2119,13 @@ int hbrbc_ba_round(const hbrbc_ba_args *a, void *stream) {
 int hbrbc_subset_round(const hbrbc_subset_args *a, void *stream) {
     if (!a) return fail(HBRBC_E_INVALID_ARG, "null argument");
     if (a->count == 0) return HBRBC_OK;
-    if (a->n == 0 || a->n > 255)
-        return fail(HBRBC_E_INVALID_ARG, "the state machine handles 1..255 validators");
-    if (a->max_out == 0 || a->queue_epochs == 0 || a->queue_epochs > 16 || a->coins == 0)
-        return fail(HBRBC_E_INVALID_ARG, "bad max_out / queue_epochs / coins");
-    if (a->round < 0) return fail(HBRBC_E_INVALID_ARG, "negative round");
-    if (!a->role || !a->flip || !a->ahead || !a->share_ok || !a->coin || !a->out ||
+    const bool missing =
+        !a->role || !a->flip || !a->ahead || !a->share_ok || !a->coin || !a->out ||
         !a->out_count || !a->state || !a->decision || !a->decision_epoch || !a->fault_count ||
         !a->output_root || !a->proposal || !a->node_state || !a->out_seq || !a->out_len ||
-        !a->emitted || (a->max_faults && !a->faults) || (a->round > 0 && (!a->in || !a->in_count)))
-        return fail(HBRBC_E_INVALID_ARG, "null argument");
-    if (int rc = have_device()) return rc;
+        !a->emitted || (a->max_faults && !a->faults) || (a->round > 0 && (!a->in || !a->in_count));
+    const char *bad = bad_agreement_limits(a->max_out, a->queue_epochs, a->coins);
+    if (int rc = round_checks(a->n, bad, a->round, missing)) return rc;
     HB_HIP(launch_subset_round(*a, static_cast<hipStream_t>(stream)));
     return HBRBC_OK;
 }
@@ -2123,16 +2134,13 @@ int hbrbc_subset_round(const hbrbc_subset_args *a, void *stream) {
 int hbrbc_hb_round(const hbrbc_hb_args *a, void *stream) {
     if (!a) return fail(HBRBC_E_INVALID_ARG, "null argument");
     if (a->count == 0) return HBRBC_OK;
-    if (a->n == 0 || a->n > 255)
-        return fail(HBRBC_E_INVALID_ARG, "the state machine handles 1..255 validators");
-    if (a->roots == 0 || a->roots > 8) return fail(HBRBC_E_INVALID_ARG, "roots must be 1..8");
-    if (a->round < 0) return fail(HBRBC_E_INVALID_ARG, "negative round");
-    if (!a->inst_flags || !a->role || !a->ct_state || !a->undeserialisable || !a->share_ok ||
+    const char *bad = a->roots == 0 || a->roots > 8 ? "roots must be 1..8" : nullptr;
+    const bool missing =
+        !a->inst_flags || !a->role || !a->ct_state || !a->undeserialisable || !a->share_ok ||
         !a->output_root || !a->out_seq || !a->out_len || !a->out || !a->node_state ||
         !a->done_round || !a->batch_round || !a->dstate || !a->mask || !a->fault_count ||
-        !a->emitted || (a->max_faults && !a->faults) || (a->round > 0 && !a->in))
-        return fail(HBRBC_E_INVALID_ARG, "null argument");
-    if (int rc = have_device()) return rc;
+        !a->emitted || (a->max_faults && !a->faults) || (a->round > 0 && !a->in);
+    if (int rc = round_checks(a->n, bad, a->round, missing)) return rc;
     HB_HIP(launch_hb_round(*a, static_cast<hipStream_t>(stream)));
     return HBRBC_OK;
 }

@@ -28,13 +28,12 @@ with the caller.
 One epoch only: several live `EpochState`s per node (`max_future_epochs`) are
 the host class's; the device runs them one after the other.
 """
-import ctypes
-
 import numpy as np
 import torch
 
-from . import _check, lib, rbc_sim, subset_sim
+from . import rbc_sim, rounds as shared, subset_sim
 from .honey_badger import ALL_AT_END, CT_INVALID, CT_VALID, INCREMENTAL, DecryptTable
+from .rounds import I32, U32, USIZE
 from .subset_sim import ROUND_BATCH
 
 HONEST, SILENT, BAD_SHARE, TWICE, STRAY, ABSENT = range(6)   # enum hbrbc_hb_role
@@ -48,26 +47,18 @@ FAULT_KINDS = ("UnexpectedDecryptionShare", "DeserializeCiphertext", "InvalidCip
                "DecryptionFault(UnverifiedDecryptionShareSender)")
 BAD_INDEX, BAD_SEQ = 1, 2
 
-_P = ctypes.c_void_p
+# hbrbc_hb_args.emitted[1] of a round, in the order the read-back looks at them
+ROUND_FLAGS = (
+    (BAD_INDEX, "honey badger: a root slot, ct_state or role out of range"),
+    (shared.ANY, "honey badger: an output sequence out of range (flags {1:#x})"))
 
-
-class HbArgs(ctypes.Structure):
-    """struct hbrbc_hb_args (include/hbrbc.h)."""
-    _fields_ = [("count", ctypes.c_size_t), ("n", ctypes.c_uint32), ("roots", ctypes.c_uint32),
-                ("max_faults", ctypes.c_uint32), ("round", ctypes.c_int32)] + [
-        (name, _P) for name in (
-            "inst_flags", "role", "ct_state", "undeserialisable", "share_ok", "output_root",
-            "out_seq", "out_len", "in_", "out", "node_state", "done_round", "batch_round", "dstate",
-            "mask", "faults", "fault_count", "emitted", "active")]
-
-
-def _bind():
-    L = lib()
-    if not getattr(L, "_hb_bound", False):
-        L.hbrbc_hb_round.restype = ctypes.c_int
-        L.hbrbc_hb_round.argtypes = [ctypes.POINTER(HbArgs), _P]
-        L._hb_bound = True
-    return L
+HbArgs = shared.args_struct(
+    "HbArgs", "hbrbc_hb_args",
+    [("count", USIZE), ("n", U32), ("roots", U32), ("max_faults", U32), ("round", I32)],
+    ("inst_flags", "role", "ct_state", "undeserialisable", "share_ok", "output_root", "out_seq",
+     "out_len", "in_", "out", "node_state", "done_round", "batch_round", "dstate", "mask",
+     "faults", "fault_count", "emitted", "active"))
+HB_ROUND = shared.Entry("hbrbc_hb_round", HbArgs)
 
 
 # ------------------------------------------------------------------ scenario --
@@ -200,7 +191,7 @@ class HbRank:
         self.max_faults = max(16, 4 * n) if hb_max_faults is None else hb_max_faults
         dev = self.device = self.sub.device
         self.sc = scn.tensors(dev)
-        _bind()
+        HB_ROUND.bind()
         B = cnt * n
         i32 = dict(dtype=torch.int32, device=dev)
         u8 = dict(dtype=torch.uint8, device=dev)
@@ -233,8 +224,6 @@ class HbRank:
             raise RuntimeError("honey badger: round %d past max_rounds %d" % (r, self.max_rounds))
         a = HbArgs(count=self.count, n=self.n, roots=self.roots, max_faults=self.max_faults,
                    round=r)
-        for name in ("inst_flags", "role", "ct_state", "undeserialisable", "share_ok"):
-            setattr(a, name, self.sc[name].data_ptr())
         a.output_root = self.sub.bc.output_root.data_ptr()
         a.out_seq, a.out_len = self.sub.out_seq.data_ptr(), self.sub.out_len.data_ptr()
         a.in_, a.out = self.inbox.data_ptr(), self.out.data_ptr()
@@ -242,64 +231,37 @@ class HbRank:
         a.batch_round, a.dstate = self.batch_round.data_ptr(), self.dstate.data_ptr()
         a.mask, a.faults = self.mask.data_ptr(), self.faults.data_ptr()
         a.fault_count = self.fault_count.data_ptr()
-        a.emitted = self.hist[r].data_ptr()
-        a.active = None if active is None else active.data_ptr()
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _check(_bind().hbrbc_hb_round(ctypes.byref(a), ctypes.c_void_p(st.cuda_stream)))
+        shared.fill(a, self.sc, self.hist, r, active)
+        HB_ROUND.launch(a, self.device, stream)
 
-    def round(self, r, events=None):
+    def round(self, r, phase=shared.call):
         """The three phases of round r, then the swap of the share records.
         Phases 1 and 2 are subset_sim.SubsetRank.round as it is (phase 3 reads
         out_seq, out_len and output_root, which the Subset's own swap leaves
         alone); once the Subset is quiescent it stays so -- nothing of phase 3
         feeds back into it -- while share records may go on for a round or
         two, so phase 3's `active` counts the records of all three protocols.
-        events: (start, end) torch events recorded around phase 3."""
+        phase: the loop's hook around every launch (rounds.Rounds)."""
         sub = self.sub
-        sub.round(r)
+        sub.round(r, phase)
         self.out.zero_()
-        if events:
-            events[0].record()
-        self.phase3(r, active=None if r == 0 else self.act[r])
-        if events:
-            events[1].record()
+        phase("phase3", self.phase3, r, None if r == 0 else self.act[r])
         torch.add(sub.act[r + 1], self.hist[r, 0], out=self.act[r + 1])
         self.inbox, self.out = self.out, self.inbox
 
 
 def run_rounds(rank, events=None):
     """Drive the three state machines until none emits a record, ROUND_BATCH
-    rounds per read-back.  Returns the number of rounds.  Every run starts
-    from fresh nodes.  events: a list that receives phase 3's (start, end)
-    event pair of every round."""
-    rank.reset()
+    rounds per read-back (rounds.Rounds).  Returns the number of rounds.
+    Every run starts from fresh nodes.  events: a list that receives (phase
+    name, start, end) device events of every launch: "phase1", "phase2" and
+    "phase3" per round."""
     sub = rank.sub
-    r = 0
-    while True:
-        hi = min(rank.max_rounds, r + ROUND_BATCH)
-        for rr in range(r, hi):
-            ev = None
-            if events is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                events.append(ev)
-            rank.round(rr, ev)
-        h = torch.stack([sub.bc.hist[r:hi], sub.hist[r:hi], rank.hist[r:hi]]).cpu().numpy()
-        for i in range(hi - r):
-            subset_sim._check_flags(sub, int(h[0, i, 1]), int(h[1, i, 1]))
-            if int(h[2, i, 1]) & BAD_INDEX:
-                raise RuntimeError("honey badger: a root slot, ct_state or role out of range")
-            if int(h[2, i, 1]):
-                raise RuntimeError("honey badger: an output sequence out of range (flags %#x)"
-                                   % int(h[2, i, 1]))
-            sub.bc_records += int(h[0, i, 0])
-            sub.ba_records += int(h[1, i, 0])
-            rank.hb_records += int(h[2, i, 0])
-            if int(h[0, i, 0]) + int(h[1, i, 0]) + int(h[2, i, 0]) == 0:
-                return r + i + 1
-        if hi >= rank.max_rounds:
-            raise RuntimeError("honey badger did not quiesce in %d rounds" % rank.max_rounds)
-        r = hi
+    return shared.Rounds(subset_sim.protocols(sub) +
+                         [shared.Protocol(ROUND_FLAGS, rank, rank, "hb_records")],
+                         rank.max_rounds, ROUND_BATCH, "honey badger", events=events,
+                         reset=rank.reset, enqueue=rank.round,
+                         read=shared.hist_rows([sub.bc, sub, rank])).launch().wait()
 
 
 class HbRun(subset_sim.SubsetRun):
@@ -314,8 +276,8 @@ class HbRun(subset_sim.SubsetRun):
         br = rank.batch_round.cpu().numpy()
         ds = rank.dstate.cpu().numpy().reshape(cnt, n, n)
         root = rank.sub.bc.output_root.cpu().numpy().reshape(cnt, n, n)
-        logs = subset_sim._fault_logs(rank.fault_count, rank.faults, rank.max_faults, FAULT_KINDS,
-                                      "honey badger")
+        logs = shared.fault_logs(rank.fault_count, rank.faults, rank.max_faults, FAULT_KINDS,
+                                 "honey badger ")
         self.batch, self.batch_round, self.hb_faults, self.dstate = {}, {}, {}, {}
         for i, inst in enumerate(scn.instances):
             for j in range(n):
@@ -354,11 +316,6 @@ def simulate(scn, device=0, **kw):
 
 
 # ------------------------------------------------------------- data plane ---
-def _i32(values, dev):
-    a = np.asarray(values, dtype=np.int64).reshape(-1).astype(np.uint32)
-    return torch.from_numpy(a.view(np.int32).copy()).to(dev)
-
-
 def decrypt_plane(scn, ciphertexts, keys, device=0, timings=None):
     """The data plane of the decryptions, on the existing entries
     (hbbft_amd/threshold.py): ciphertexts[inst * n + p] = (U compressed G1, 48
@@ -375,6 +332,7 @@ def decrypt_plane(scn, ciphertexts, keys, device=0, timings=None):
     info: share_tab / share_count / items for further combines.  timings: a
     dict that receives the milliseconds of the four steps."""
     from . import threshold as T
+    u32 = T._u32_tensor
     n, cnt = scn.n, scn.count
     C = len(ciphertexts)
     if C != cnt * n or scn.roots != 1 or n < 2:
@@ -409,11 +367,11 @@ def decrypt_plane(scn, ciphertexts, keys, device=0, timings=None):
     other = [(c // n) * n + (c % n + 1) % n for c in range(C)]
     hw = torch.stack([T._g2_rows([h for _, _, h in ciphertexts], dev), w192], dim=1)
     prep = T.g2_prepare(hw.reshape(2 * C, T.G2_BYTES).contiguous())
-    idx_b, idx_d = _i32([2 * c for c in items], dev), _i32([2 * c + 1 for c in items], dev)
-    ok0 = T.pairing_check_prepared_keys(s96.contiguous(), pk_tab, n, _i32(nodes, dev), prep, 2 * C,
+    idx_b, idx_d = u32([2 * c for c in items], dev), u32([2 * c + 1 for c in items], dev)
+    ok0 = T.pairing_check_prepared_keys(s96.contiguous(), pk_tab, n, u32(nodes, dev), prep, 2 * C,
                                         idx_b, idx_d)
-    swapped = s96[_i32([T.share_row(i, other[c], C) for i, c in zip(nodes, items)], dev).long()]
-    ok1 = T.pairing_check_prepared_keys(swapped.contiguous(), pk_tab, n, _i32(nodes, dev), prep,
+    swapped = s96[u32([T.share_row(i, other[c], C) for i, c in zip(nodes, items)], dev).long()]
+    ok1 = T.pairing_check_prepared_keys(swapped.contiguous(), pk_tab, n, u32(nodes, dev), prep,
                                         2 * C, idx_b, idx_d)
     # [node][item] -> [item][slot 0][variant][node]
     share_ok = torch.stack([(o == T.CHECK_OK).to(torch.uint8).view(n, C).t() for o in (ok0, ok1)],
@@ -434,11 +392,12 @@ def decrypt_combine(info, nodes, dev):
     """Combine the shares of `nodes` (f + 1 distinct node indices) for every
     ciphertext of a decrypt_plane: g compressed, uint8 [items][48]."""
     from . import threshold as T
+    u32 = T._u32_tensor
     C, k = info["items"], len(nodes)
     rows = [T.share_row(i, c, C) for c in range(C) for i in nodes]
-    offs = _i32(np.arange(C + 1) * k, dev)
+    offs = u32(np.arange(C + 1) * k, dev)
     _, g48, st = T.decrypt_combine_prepared(info["share_tab"], info["share_count"],
-                                            _i32(rows, dev), _i32(list(nodes) * C, dev), offs)
+                                            u32(rows, dev), u32(list(nodes) * C, dev), offs)
     if st.cpu().numpy().any():
         raise ValueError("decrypt_plane: a combine failed")
     return g48

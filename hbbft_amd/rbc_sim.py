@@ -30,12 +30,11 @@ faulty nodes' own value.  tests/test_rbc_sim.py checks every node's output and
 fault log against the host restatement (hbbft_amd/broadcast.py driven by
 tests/virtual_net.py RoundNet) on the same scenarios.
 """
-import ctypes
-
+import numpy as np
 import torch
 
-from . import _check, decode_shards_batch, lib, send_shards_batch, validate_proofs
-from . import RbcBatch
+from . import RbcBatch, decode_shards_batch, rounds as shared, send_shards_batch, validate_proofs
+from .rounds import I32, U32, USIZE
 
 NONE = 0xFF
 HONEST, SILENT, CORRUPT_ECHO, WITHHOLD_ECHO = 0, 1, 2, 3
@@ -44,23 +43,23 @@ FAULT_KINDS = ["ReceivedValueFromNonProposer", "MultipleValues", "MultipleEchos"
                "MultipleEchoHashes", "MultipleReadys", "InvalidProof", "BroadcastDecoding"]
 MSG_KINDS = ["Value", "Echo", "Ready", "CanDecode", "EchoHash", "Fake"]
 
-_P = ctypes.c_void_p
-
-
-class SmArgs(ctypes.Structure):
-    """struct hbrbc_sm_args (include/hbrbc.h)."""
-    _fields_ = [("count", ctypes.c_size_t), ("node_lo", ctypes.c_uint32),
-                ("nodes", ctypes.c_uint32), ("rows_per_rank", ctypes.c_uint32),
-                ("roots", ctypes.c_uint32), ("max_out", ctypes.c_uint32),
-                ("max_faults", ctypes.c_uint32), ("round", ctypes.c_int32)] + [
-        (name, _P) for name in (
-            "proposer", "role", "value_root", "value_tamper", "proof_ok", "decode_ok",
-            "fake_from", "fake_root", "fake_list", "in_", "in_count", "out", "out_count",
-            "state", "output_root", "faults", "fault_count", "emitted", "active")] + [
-        ("flags", ctypes.c_uint32)]
-
+SmArgs = shared.args_struct(
+    "SmArgs", "hbrbc_sm_args",
+    [("count", USIZE), ("node_lo", U32), ("nodes", U32), ("rows_per_rank", U32), ("roots", U32),
+     ("max_out", U32), ("max_faults", U32), ("round", I32)],
+    ("proposer", "role", "value_root", "value_tamper", "proof_ok", "decode_ok", "fake_from",
+     "fake_root", "fake_list", "in_", "in_count", "out", "out_count", "state", "output_root",
+     "faults", "fault_count", "emitted", "active"),
+    [("flags", U32)])
+# the context handle first; launched without a device guard (the handle's device)
+SM_ROUND = shared.Entry("hbrbc_sm_round", SmArgs, handle=True, sizes=("hbrbc_sm_state_bytes",))
 
 SM_NO_FAKE = 1   # hbrbc_sm_args.flags: no instance injects broadcasts (HBRBC_SM_NO_FAKE)
+# hbrbc_sm_args.emitted[1] of a round, in the order the read-back looks at them
+ROUND_FLAGS = (
+    (2, "state machine: a Value / Fake record or a fake_from node reached a round run without "
+        "those handlers (hbrbc_sm_args.flags)"),
+    (shared.ANY, "state machine: a node emitted more than {0.max_out} messages in a round"))
 
 
 def sm_state_bytes_host(n, roots):
@@ -73,17 +72,6 @@ def sm_state_bytes_host(n, roots):
     er = 16 * w if roots == 1 else 2 * n
     full = 0 if roots == 1 else 4 * w
     return (er + 4 * roots * w + full + 6 * roots + 4 + 6 + 15) & ~15
-
-
-def _bind():
-    L = lib()
-    if not getattr(L, "_sm_bound", False):
-        L.hbrbc_sm_state_bytes.restype = ctypes.c_size_t
-        L.hbrbc_sm_state_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t]
-        L.hbrbc_sm_round.restype = ctypes.c_int
-        L.hbrbc_sm_round.argtypes = [_P, ctypes.POINTER(SmArgs), _P]
-        L._sm_bound = True
-    return L
 
 
 # ------------------------------------------------------------------ scenario --
@@ -131,7 +119,6 @@ class Scenario:
         vt = torch.tensor([i.value_tamper for i in self.instances], **u8).view(cnt, n)
         ff = torch.tensor([NONE if i.fake_from is None else i.fake_from for i in self.instances], **u8)
         fr = torch.tensor([0 if i.fake_root is None else i.fake_root for i in self.instances], **u8)
-        import numpy as np
         flw = np.zeros((cnt, W), np.uint32)
         for r, i in enumerate(self.instances):
             for F in i.fake_list:
@@ -227,8 +214,7 @@ class StateMachineRank:
         self.rb = RbcBatch(n, device=device)
         dev = self.rb.device
         self.device = dev
-        L = _bind()
-        sb = L.hbrbc_sm_state_bytes(n, roots)
+        sb = SM_ROUND.bind().hbrbc_sm_state_bytes(n, roots)
         R, cnt = self.R, count
         self.sc = sc
         # no fake_from node anywhere: rounds >= 2 run the kernels without the
@@ -278,23 +264,16 @@ class StateMachineRank:
         0 (quiescent), so rounds can be enqueued without reading back."""
         if r >= self.max_rounds:
             raise RuntimeError("state machine: round %d past max_rounds %d" % (r, self.max_rounds))
-        s = self.sc
         a = SmArgs(count=self.count, node_lo=self.node_lo, nodes=self.R, rows_per_rank=self.R,
                    roots=self.roots, max_out=self.max_out, max_faults=self.max_faults, round=r,
                    flags=self.flags)
-        for name in ("proposer", "role", "value_root", "value_tamper", "fake_from", "fake_root",
-                     "fake_list"):
-            setattr(a, name, s[name].data_ptr())
         a.proof_ok, a.decode_ok = self.ok.data_ptr(), self.dec.data_ptr()
         a.in_, a.in_count = self.inbox.data_ptr(), self.inbox_count.data_ptr()
         a.out, a.out_count = self.out.data_ptr(), self.out_count.data_ptr()
         a.state, a.output_root = self.state.data_ptr(), self.output_root.data_ptr()
         a.faults, a.fault_count = self.faults.data_ptr(), self.fault_count.data_ptr()
-        a.emitted = self.hist[r].data_ptr()
-        a.active = None if active is None else active.data_ptr()
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _check(_bind().hbrbc_sm_round(self.rb.coding.handle, ctypes.byref(a),
-                                      ctypes.c_void_p(st.cuda_stream)))
+        shared.fill(a, self.sc, self.hist, r, active)
+        SM_ROUND.launch(a, self.device, stream, self.rb.coding.handle)
 
     def emitted(self, r):
         """Device int32 scalar: records this rank emitted in round r."""
@@ -313,19 +292,8 @@ class StateMachineRank:
 
     def fault_logs(self):
         """{(inst, node): [(blamed node, FaultKind name)]} of the hosted nodes."""
-        fc = self.fault_count.cpu().numpy()
-        fl = self.faults.cpu().numpy().astype("uint16")
-        out = {}
-        for i in range(self.count):
-            for r in range(self.R):
-                node = self.node_lo + r
-                if node >= self.n:
-                    continue
-                cnt = int(fc[i, r])
-                if cnt > self.max_faults:
-                    raise RuntimeError("fault log overflow at (%d, %d): %d records" % (i, node, cnt))
-                out[(i, node)] = [(int(v) >> 8, FAULT_KINDS[int(v) & 0xFF]) for v in fl[i, r, :cnt]]
-        return out
+        return shared.fault_logs(self.fault_count, self.faults, self.max_faults, FAULT_KINDS,
+                                 node_lo=self.node_lo, n=self.n)
 
 
 class LoopbackExchange:
@@ -345,37 +313,22 @@ class LoopbackExchange:
 ROUND_BATCH = 6   # rounds enqueued per read-back (honest runs quiesce after 5)
 
 
-def _check_batch(ranks, h, r0, own=None):
-    """h [ranks][rounds][2] (host) of rounds r0..: records per round and the
-    overflow flags; returns the number of rounds run if one of them was
-    quiescent (no records anywhere), else None.  own: the records of THIS
-    rank per (sub-batch, round) where h holds every rank's totals."""
-    for i in range(h.shape[1]):
-        fl = int(h[:, i, 1].max())
-        if fl & 2:
-            raise RuntimeError("state machine: a Value / Fake record or a fake_from node reached "
-                               "a round run without those handlers (hbrbc_sm_args.flags)")
-        if fl:
-            raise RuntimeError("state machine: a node emitted more than %d messages in a round"
-                               % ranks[0].max_out)
-        mine = h[:, i, 0] if own is None else own[:, i]
-        for sm, c in zip(ranks, mine):
-            sm.records += int(c)
-        if int(h[:, i, 0].sum()) == 0:
-            return r0 + i + 1
-    return None
+def _protocols(ranks):
+    """The read-back's part of every rank (or sub-batch): the flags raise by
+    ROUND_FLAGS, naming the first one's limits; each tallies its `records`."""
+    return [shared.Protocol(ROUND_FLAGS, ranks[0], sm, "records") for sm in ranks]
 
 
-class LocalRounds:
+class LocalRounds(shared.Rounds):
     """The rounds of the StateMachineRank objects of one process with no
     process group -- the virtual ranks of a loopback topology (loopback=True:
     their records are gathered between rounds) or independent objects each
     talking to itself -- split into enqueue and read-back so a caller can
-    overlap them with other work: `launch()` enqueues the first ROUND_BATCH
-    rounds on `stream` (default: the current stream) and returns at once;
-    `wait()` reads the per-round counts back (one host read, synchronising
-    that stream only), enqueues and reads further batches until the network
-    is quiescent, and returns the number of rounds.
+    overlap them with other work (rounds.Rounds): `launch()` enqueues the
+    first ROUND_BATCH rounds on `stream` (default: the current stream) and
+    returns at once; `wait()` reads the per-round counts back (one host read,
+    synchronising that stream only), enqueues and reads further batches until
+    the network is quiescent, and returns the number of rounds.
 
     Round r gets the device total of round r - 1's records as `active` and
     returns at once when it is 0, so the rounds past quiescence cost an empty
@@ -384,67 +337,38 @@ class LocalRounds:
 
     def __init__(self, ranks, loopback, max_rounds=64, stream=None):
         self.ranks = ranks
-        self.max_rounds = min(max_rounds, min(sm.max_rounds for sm in ranks))
         self.loop = LoopbackExchange(ranks) if loopback and len(ranks) > 1 else None
-        self.stream = stream
-        dev = ranks[0].device
+        max_rounds = min(max_rounds, min(sm.max_rounds for sm in ranks))
         # with a loopback the next round's flag is the total over all ranks
-        self.act = torch.zeros(self.max_rounds + 1, dtype=torch.int32, device=dev) \
+        self.act = torch.zeros(max_rounds + 1, dtype=torch.int32, device=ranks[0].device) \
             if self.loop is not None else None
-        self.next = 0
+        super().__init__(_protocols(ranks), max_rounds, ROUND_BATCH, "state machine", stream)
 
-    def _enqueue(self, r, hi):
+    def read(self, r, hi):   # a flag of any rank fails the run
+        h, total = shared.hist_rows(self.ranks)(r, hi)
+        if len(self.ranks) > 1:
+            h[:, :, 1] = h[:, :, 1].max(axis=0)
+        return h, total
+
+    def reset(self):
+        for sm in self.ranks:
+            sm.reset()
+
+    def enqueue(self, rr, phase):
         ranks, act = self.ranks, self.act
-        for rr in range(r, hi):
+        for sm in ranks:
+            if rr == 0:
+                phase("broadcast", sm.round, 0)
+            else:   # own count (independent objects) or the device total
+                phase("broadcast", sm.round, rr,
+                      sm.emitted(rr - 1) if act is None else act[rr])
+        if act is not None:
+            act[rr + 1].copy_(torch.stack([sm.emitted(rr) for sm in ranks]).sum())
+        if self.loop is not None:
+            self.loop.gather()
+        else:
             for sm in ranks:
-                if rr == 0:
-                    sm.round(0)
-                else:   # own count (independent objects) or the device total
-                    sm.round(rr, active=sm.emitted(rr - 1) if act is None else act[rr])
-            if act is not None:
-                act[rr + 1].copy_(torch.stack([sm.emitted(rr) for sm in ranks]).sum())
-            if self.loop is not None:
-                self.loop.gather()
-            else:
-                for sm in ranks:
-                    sm.swap_local()
-        self.next = hi
-
-    def _ctx(self):
-        return torch.cuda.stream(self.stream) if self.stream is not None else _nullctx()
-
-    def launch(self):
-        """Every run starts from fresh nodes: the per-round counts (hist) are
-        accumulated by the kernel, and the inbox of the rounds after the last
-        quiescent one still holds records, so a run never continues another."""
-        with self._ctx():
-            for sm in self.ranks:
-                sm.reset()
-            self._enqueue(0, min(self.max_rounds, ROUND_BATCH))
-        return self
-
-    def wait(self):
-        r = 0   # first round whose count has not been read
-        with self._ctx():
-            while True:
-                hi = self.next
-                h = torch.stack([sm.hist[r:hi] for sm in self.ranks]).cpu()   # one read
-                done = _check_batch(self.ranks, h, r)
-                if done is not None:
-                    return done
-                if hi >= self.max_rounds:
-                    raise RuntimeError("state machine did not quiesce in %d rounds"
-                                       % self.max_rounds)
-                self._enqueue(hi, min(self.max_rounds, hi + ROUND_BATCH))
-                r = hi
-
-
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
+                sm.swap_local()
 
 
 def run_rounds(ranks, exchange=None, max_rounds=64):
@@ -460,7 +384,7 @@ def run_rounds(ranks, exchange=None, max_rounds=64):
     return LocalRounds(ranks, loopback=exchange is None, max_rounds=max_rounds).launch().wait()
 
 
-class DistRounds:
+class DistRounds(shared.Rounds):
     """run_rounds over a process group, split into enqueue and read-back like
     LocalRounds so a caller can overlap the rounds with other work (the
     validator-sharded step pipelines at world > 1, sharded.OverlapPipe):
@@ -477,73 +401,55 @@ class DistRounds:
     concurrently on another stream."""
 
     def __init__(self, ranks, ex, max_rounds=64, stream=None):
-        self.ranks, self.ex, self.stream = ranks, ex, stream
-        self.max_rounds = min(max_rounds, min(sm.max_rounds for sm in ranks))
-        self.next = 0
+        self.ranks, self.ex = ranks, ex
+        super().__init__(_protocols(ranks), min(max_rounds, min(sm.max_rounds for sm in ranks)),
+                         ROUND_BATCH, "state machine", stream)
 
-    def _ctx(self):
-        return torch.cuda.stream(self.stream) if self.stream is not None else _nullctx()
-
-    def _enqueue(self, r, hi):
-        ranks, ex = self.ranks, self.ex
-        send, recv, body, k = self.send, self.recv, self.body, len(ranks)
-        for rr in range(r, hi):
-            for sm in ranks:
-                sm.round(rr, active=None if rr == 0 else self.act[rr])
-            off = 0
-            for sm, (a, b) in zip(ranks, self.parts):
-                send[off:off + a].copy_(sm.out.view(-1))
-                send[off + a:off + a + b].copy_(sm.out_count.view(-1))
-                off += a + b
-            hist = torch.stack([sm.hist[rr] for sm in ranks])       # [k][2]
-            send[body:body + k].copy_(hist[:, 0])
-            send[body + k:].copy_(hist[:, 1].amax().view(1))
-            ex.all_gather(recv, send, name="sm_round")
-            self.tails[rr].copy_(recv[:, body:])
-            self.act[rr + 1].copy_(recv[:, body:body + k].sum())
-            off = 0
-            for sm, (a, b) in zip(ranks, self.parts):
-                sm.inbox.view(ex.world, a).copy_(recv[:, off:off + a])
-                sm.inbox_count.view(ex.world, b).copy_(recv[:, off + a:off + a + b])
-                off += a + b
-        self.next = hi
-
-    def launch(self):
-        """Fresh nodes (every run), then the first batch of rounds."""
+    def reset(self):
+        """Fresh nodes, and the buffers of the fused all-gather."""
         ranks, ex = self.ranks, self.ex
         dev = ranks[0].device
-        with self._ctx():
-            for sm in ranks:
-                sm.reset()
-            self.parts = [(sm.out.numel(), sm.out_count.numel()) for sm in ranks]
-            k = len(ranks)
-            self.body = sum(a + b for a, b in self.parts)
-            self.send = torch.zeros(self.body + k + 1, dtype=torch.int32, device=dev)
-            self.recv = torch.empty((ex.world, self.body + k + 1), dtype=torch.int32, device=dev)
-            self.tails = torch.zeros((self.max_rounds, ex.world, k + 1), dtype=torch.int32,
-                                     device=dev)
-            self.act = torch.zeros(self.max_rounds + 1, dtype=torch.int32, device=dev)
-            self._enqueue(0, min(self.max_rounds, ROUND_BATCH))
-        return self
+        for sm in ranks:
+            sm.reset()
+        self.parts = [(sm.out.numel(), sm.out_count.numel()) for sm in ranks]
+        k = len(ranks)
+        self.body = sum(a + b for a, b in self.parts)
+        self.send = torch.zeros(self.body + k + 1, dtype=torch.int32, device=dev)
+        self.recv = torch.empty((ex.world, self.body + k + 1), dtype=torch.int32, device=dev)
+        self.tails = torch.zeros((self.max_rounds, ex.world, k + 1), dtype=torch.int32,
+                                 device=dev)
+        self.act = torch.zeros(self.max_rounds + 1, dtype=torch.int32, device=dev)
 
-    def wait(self):
-        ranks, ex, k = self.ranks, self.ex, len(self.ranks)
-        r = 0
-        with self._ctx():
-            while True:
-                hi = self.next
-                t = self.tails[r:hi].cpu()                          # [rounds][world][k + 1]
-                # every rank's per-round totals (records of all ranks, overflow of any)
-                h = torch.stack([t[:, :, :k].sum(dim=1).sum(dim=1), t[:, :, k].amax(dim=1)], dim=1)
-                own = t[:, ex.rank, :k].transpose(0, 1)             # [k][rounds]
-                done = _check_batch(ranks, h.unsqueeze(0), r, own=own)
-                if done is not None:
-                    return done
-                if hi >= self.max_rounds:
-                    raise RuntimeError("state machine did not quiesce in %d rounds"
-                                       % self.max_rounds)
-                self._enqueue(hi, min(self.max_rounds, hi + ROUND_BATCH))
-                r = hi
+    def enqueue(self, rr, phase):
+        ranks, ex = self.ranks, self.ex
+        send, recv, body, k = self.send, self.recv, self.body, len(ranks)
+        for sm in ranks:
+            phase("broadcast", sm.round, rr, None if rr == 0 else self.act[rr])
+        off = 0
+        for sm, (a, b) in zip(ranks, self.parts):
+            send[off:off + a].copy_(sm.out.view(-1))
+            send[off + a:off + a + b].copy_(sm.out_count.view(-1))
+            off += a + b
+        hist = torch.stack([sm.hist[rr] for sm in ranks])       # [k][2]
+        send[body:body + k].copy_(hist[:, 0])
+        send[body + k:].copy_(hist[:, 1].amax().view(1))
+        ex.all_gather(recv, send, name="sm_round")
+        self.tails[rr].copy_(recv[:, body:])
+        self.act[rr + 1].copy_(recv[:, body:body + k].sum())
+        off = 0
+        for sm, (a, b) in zip(ranks, self.parts):
+            sm.inbox.view(ex.world, a).copy_(recv[:, off:off + a])
+            sm.inbox_count.view(ex.world, b).copy_(recv[:, off + a:off + a + b])
+            off += a + b
+
+    def read(self, r, hi):
+        """The gathered tails [rounds][world][k + 1] of rounds r..hi: every
+        sub-batch tallies THIS rank's records, the flag of any rank fails the
+        run, and the records of all ranks decide quiescence."""
+        k = len(self.ranks)
+        t = self.tails[r:hi].cpu().numpy()
+        flags = np.broadcast_to(t[:, :, k].max(axis=1), (k, hi - r))
+        return np.stack([t[:, self.ex.rank, :k].T, flags], axis=2), t[:, :, :k].sum(axis=(1, 2))
 
 
 def _run_rounds_dist(ranks, ex, max_rounds):

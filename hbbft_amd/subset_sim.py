@@ -27,12 +27,11 @@ WITHHOLD_ECHO nodes; no injected broadcasts), per node an agreement role
 (ba_sim), and dead nodes: a dead node never proposes and emits nothing in any
 sub-protocol; all its proposal states start dropped.
 """
-import ctypes
-
 import numpy as np
 import torch
 
-from . import _check, ba_sim, lib, rbc_sim
+from . import ba_sim, rbc_sim, rounds as shared
+from .rounds import I32, U32, USIZE
 
 NONE = 0xFF
 DROPPED = 0xFE            # HBRBC_SM_DROPPED
@@ -42,27 +41,27 @@ SM_SUBSET = 2             # HBRBC_SM_SUBSET
 # the proposal-state byte (enum hbrbc_subset_proposal)
 PS_ONGOING, PS_HAS_VALUE, PS_ACCEPTED, PS_COMPLETE_FALSE, PS_COMPLETE_TRUE = range(5)
 
-_P = ctypes.c_void_p
+SubsetArgs = shared.args_struct(
+    "SubsetArgs", "hbrbc_subset_args",
+    [("count", USIZE), ("n", U32), ("max_out", U32), ("max_faults", U32), ("queue_epochs", U32),
+     ("coins", U32), ("round", I32)],
+    ("role", "flip", "ahead", "share_ok", "coin", "in_", "in_count", "out", "out_count", "state",
+     "decision", "decision_epoch", "faults", "fault_count", "output_root", "proposal",
+     "node_state", "out_seq", "out_len", "emitted", "active"))
+SUBSET_ROUND = shared.Entry("hbrbc_subset_round", SubsetArgs)
 
-
-class SubsetArgs(ctypes.Structure):
-    """struct hbrbc_subset_args (include/hbrbc.h)."""
-    _fields_ = [("count", ctypes.c_size_t), ("n", ctypes.c_uint32), ("max_out", ctypes.c_uint32),
-                ("max_faults", ctypes.c_uint32), ("queue_epochs", ctypes.c_uint32),
-                ("coins", ctypes.c_uint32), ("round", ctypes.c_int32)] + [
-        (name, _P) for name in (
-            "role", "flip", "ahead", "share_ok", "coin", "in_", "in_count", "out", "out_count",
-            "state", "decision", "decision_epoch", "faults", "fault_count", "output_root",
-            "proposal", "node_state", "out_seq", "out_len", "emitted", "active")]
-
-
-def _bind():
-    L = lib()
-    if not getattr(L, "_subset_bound", False):
-        L.hbrbc_subset_round.restype = ctypes.c_int
-        L.hbrbc_subset_round.argtypes = [ctypes.POINTER(SubsetArgs), _P]
-        L._subset_bound = True
-    return L
+# the flags of both sides of a round (hbrbc_sm_args.emitted[1], then
+# hbrbc_subset_args.emitted[1]), in the order the read-back looks at them
+BC_ROUND_FLAGS = (
+    (2, "subset: a Value / Fake record reached a broadcast round run without those handlers"),
+    (shared.ANY, "subset: a node emitted more than {0.max_out} broadcast messages in a round"))
+BA_ROUND_FLAGS = (
+    (ba_sim.BAD_QUEUE, "subset: an agreement message for an epoch beyond the future-epoch ring "
+                       "of {0.queue_epochs} slots (raise queue_epochs)"),
+    (ba_sim.BAD_COINS, "subset: a node reached a coin slot past the {0.coins} of the tables"),
+    (ba_sim.BAD_OUT, "subset: a node emitted more than {0.max_out} agreement messages in a "
+                     "round"),
+    (shared.ANY, "subset: internal limit hit (flags {1:#x})"))
 
 
 # ------------------------------------------------------------------ scenario --
@@ -152,7 +151,7 @@ class Scenario:
 
 
 # ------------------------------------------------------------- one rank -----
-class SubsetRank:
+class SubsetRank(shared.HasAgreement):
     """Every node of `count` Subset instances on one GPU (world = 1).  ok /
     dec: the data plane's proof_ok and decode_ok over the count x n broadcast
     instances."""
@@ -161,8 +160,6 @@ class SubsetRank:
                  ba_max_faults=None, queue_epochs=None, max_rounds=256):
         n, cnt = scn.n, scn.count
         self.n, self.count, self.coins = n, cnt, scn.coins
-        self.W = (n + 31) // 32
-        self.rec = 1 + self.W
         self.max_out = max_out
         self.max_faults = max(64, 8 * n) if ba_max_faults is None else ba_max_faults
         self.queue_epochs = queue_epochs or scn.queue_epochs
@@ -177,19 +174,12 @@ class SubsetRank:
         self.bc.flags |= SM_SUBSET
         self.dead = scn.dead_mask().to(dev)
         self.sc = scn.ba_scenario().tensors(dev)
-        sb = ba_sim._bind().hbrbc_ba_state_bytes(n, self.queue_epochs)
-        _bind()
+        del self.sc["input"]   # hbrbc_subset_args has none: the Subset proposes
+        SUBSET_ROUND.bind()
         i32 = dict(dtype=torch.int32, device=dev)
         u8 = dict(dtype=torch.uint8, device=dev)
-        self.state = torch.zeros((B, n, sb), **u8)
-        self.out = torch.zeros((B, n, max_out, self.rec), **i32)
-        self.out_count = torch.zeros((B, n), **i32)
-        self.inbox = torch.zeros((B, n, max_out, self.rec), **i32)
-        self.inbox_count = torch.zeros((B, n), **i32)
-        self.decision = torch.full((B, n), NONE, **u8)
-        self.decision_epoch = torch.zeros((B, n), dtype=torch.int16, device=dev)
-        self.faults = torch.zeros((B, n, max(1, self.max_faults)), dtype=torch.int16, device=dev)
-        self.fault_count = torch.zeros((B, n), **i32)
+        self.ag = shared.AgreementState(B, n, ba_sim.state_bytes(n, self.queue_epochs), max_out,
+                                        self.max_faults, dev)
         self.proposal = torch.zeros((B, n), **u8)
         self.node_state = torch.zeros((cnt, n), **i32)
         self.out_seq = torch.zeros((cnt, n, n + 1), **u8)
@@ -205,116 +195,60 @@ class SubsetRank:
         states start dropped."""
         self.bc.reset()
         self.bc.output_root.masked_fill_(self.dead, DROPPED)
-        for t in (self.state, self.out_count, self.inbox_count, self.decision_epoch,
-                  self.fault_count, self.proposal, self.node_state, self.out_seq, self.out_len,
-                  self.hist, self.act):
+        self.ag.reset()
+        for t in (self.proposal, self.node_state, self.out_seq, self.out_len, self.hist, self.act):
             t.zero_()
-        self.decision.fill_(NONE)
         self.bc_records = self.ba_records = 0
-
-    def swap_local(self):
-        self.inbox, self.out = self.out, self.inbox
-        self.inbox_count, self.out_count = self.out_count, self.inbox_count
 
     def phase2(self, r, active=None, stream=None):
         """hbrbc_subset_round of round r (after phase 1 of the same round)."""
         if r >= self.max_rounds:
             raise RuntimeError("subset: round %d past max_rounds %d" % (r, self.max_rounds))
-        s = self.sc
         a = SubsetArgs(count=self.count, n=self.n, max_out=self.max_out,
                        max_faults=self.max_faults, queue_epochs=self.queue_epochs,
                        coins=self.coins, round=r)
-        for name in ("role", "flip", "ahead", "share_ok", "coin"):
-            setattr(a, name, s[name].data_ptr())
-        a.in_, a.in_count = self.inbox.data_ptr(), self.inbox_count.data_ptr()
-        a.out, a.out_count = self.out.data_ptr(), self.out_count.data_ptr()
-        a.state = self.state.data_ptr()
-        a.decision, a.decision_epoch = self.decision.data_ptr(), self.decision_epoch.data_ptr()
-        a.faults, a.fault_count = self.faults.data_ptr(), self.fault_count.data_ptr()
+        self.ag.write(a)
         a.output_root = self.bc.output_root.data_ptr()
         a.proposal, a.node_state = self.proposal.data_ptr(), self.node_state.data_ptr()
         a.out_seq, a.out_len = self.out_seq.data_ptr(), self.out_len.data_ptr()
-        a.emitted = self.hist[r].data_ptr()
-        a.active = None if active is None else active.data_ptr()
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _check(_bind().hbrbc_subset_round(ctypes.byref(a), ctypes.c_void_p(st.cuda_stream)))
+        shared.fill(a, self.sc, self.hist, r, active)
+        SUBSET_ROUND.launch(a, self.device, stream)
 
-    def round(self, r):
+    def round(self, r, phase=shared.call):
         """Both phases of round r, then the swap of both sides' buffers.  The
         broadcasts quiesce rounds before the agreements do, and a round kernel
         that returns on `active == 0` leaves its out_count untouched: the
         broadcast side's counts are cleared before every round, so the swap
-        after a round it skipped delivers nothing."""
+        after a round it skipped delivers nothing.  phase: the loop's hook around
+        every launch (rounds.Rounds)."""
         bc = self.bc
         bc.out_count.zero_()
-        bc.round(r, active=None if r == 0 else bc.emitted(r - 1))
-        self.phase2(r, active=None if r == 0 else self.act[r])
+        phase("phase1", bc.round, r, None if r == 0 else bc.emitted(r - 1))
+        phase("phase2", self.phase2, r, None if r == 0 else self.act[r])
         torch.add(bc.hist[r, 0], self.hist[r, 0], out=self.act[r + 1])
         bc.swap_local()
-        self.swap_local()
+        self.ag.swap()
 
 
 ROUND_BATCH = 8   # rounds enqueued per read-back
 
 
-def _check_flags(rank, bc_fl, ba_fl):
-    if bc_fl & 2:
-        raise RuntimeError("subset: a Value / Fake record reached a broadcast round run without "
-                           "those handlers")
-    if bc_fl:
-        raise RuntimeError("subset: a node emitted more than %d broadcast messages in a round"
-                           % rank.max_out)
-    if ba_fl & ba_sim.BAD_QUEUE:
-        raise RuntimeError("subset: an agreement message for an epoch beyond the future-epoch "
-                           "ring of %d slots (raise queue_epochs)" % rank.queue_epochs)
-    if ba_fl & ba_sim.BAD_COINS:
-        raise RuntimeError("subset: a node reached a coin slot past the %d of the tables"
-                           % rank.coins)
-    if ba_fl & ba_sim.BAD_OUT:
-        raise RuntimeError("subset: a node emitted more than %d agreement messages in a round"
-                           % rank.max_out)
-    if ba_fl:
-        raise RuntimeError("subset: internal limit hit (flags %#x)" % ba_fl)
+def protocols(rank):
+    """The read-back's part of both sides of a SubsetRank, broadcasts first."""
+    return [shared.Protocol(BC_ROUND_FLAGS, rank, rank, "bc_records"),
+            shared.Protocol(BA_ROUND_FLAGS, rank, rank, "ba_records")]
 
 
-def run_rounds(rank):
-    """Drive both state machines until neither emits a record: batches of
-    ROUND_BATCH rounds are enqueued and the per-round counts and flags of both
-    sides read back once per batch.  Returns the number of rounds (the index
-    of the first round without records + 1).  Every run starts from fresh
-    nodes."""
-    rank.reset()
-    r = 0
-    while True:
-        hi = min(rank.max_rounds, r + ROUND_BATCH)
-        for rr in range(r, hi):
-            rank.round(rr)
-        h = torch.stack([rank.bc.hist[r:hi], rank.hist[r:hi]]).cpu().numpy()   # one read
-        for i in range(hi - r):
-            _check_flags(rank, int(h[0, i, 1]), int(h[1, i, 1]))
-            rank.bc_records += int(h[0, i, 0])
-            rank.ba_records += int(h[1, i, 0])
-            if int(h[0, i, 0]) + int(h[1, i, 0]) == 0:
-                return r + i + 1
-        if hi >= rank.max_rounds:
-            raise RuntimeError("subset did not quiesce in %d rounds" % rank.max_rounds)
-        r = hi
-
-
-def _fault_logs(counts, logs, max_faults, kinds, what):
-    """{(instance, node): [(blamed node, FaultKind name)]} of one side."""
-    fc = counts.cpu().numpy()
-    fl = logs.cpu().numpy().view(np.uint16)
-    out = {}
-    for b in range(fc.shape[0]):
-        for j in range(fc.shape[1]):
-            c = int(fc[b, j])
-            if c > max_faults:
-                raise RuntimeError("%s fault log overflow at (%d, %d): %d records"
-                                   % (what, b, j, c))
-            out[(b, j)] = [(int(v) >> 8, kinds[int(v) & 0xFF]) for v in fl[b, j, :c]]
-    return out
+def run_rounds(rank, events=None):
+    """Drive both state machines until neither emits a record (rounds.Rounds):
+    batches of ROUND_BATCH rounds are enqueued and the per-round counts and
+    flags of both sides read back once per batch.  Returns the number of
+    rounds (the index of the first round without records + 1).  Every run
+    starts from fresh nodes.  events: a list that receives (phase name, start,
+    end) device events of every launch, "phase1" and "phase2" per round."""
+    return shared.Rounds(protocols(rank), rank.max_rounds, ROUND_BATCH, "subset", events=events,
+                         reset=rank.reset, enqueue=rank.round,
+                         read=shared.hist_rows([rank.bc, rank])).launch().wait()
 
 
 class SubsetRun:
@@ -331,10 +265,10 @@ class SubsetRun:
         prop = rank.proposal.cpu().numpy().reshape(cnt, n, n)
         dec = rank.decision.cpu().numpy().reshape(cnt, n, n)
         ep = rank.decision_epoch.cpu().numpy().view(np.uint16).reshape(cnt, n, n)
-        bcf = _fault_logs(rank.bc.fault_count[:, :n], rank.bc.faults, rank.bc.max_faults,
-                          rbc_sim.FAULT_KINDS, "broadcast")
-        baf = _fault_logs(rank.fault_count, rank.faults, rank.max_faults, ba_sim.FAULT_KINDS,
-                          "agreement")
+        bcf = shared.fault_logs(rank.bc.fault_count[:, :n], rank.bc.faults, rank.bc.max_faults,
+                                rbc_sim.FAULT_KINDS, "broadcast ")
+        baf = shared.fault_logs(rank.fault_count, rank.faults, rank.max_faults,
+                                ba_sim.FAULT_KINDS, "agreement ")
         self.outputs, self.accepted = {}, {}
         self.decisions, self.decision_epochs, self.bc_faults, self.ba_faults = {}, {}, {}, {}
         for i in range(cnt):

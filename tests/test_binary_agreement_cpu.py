@@ -4,12 +4,9 @@ asynchronous random-order network and under the synchronous rounds of the GPU
 state machine (tests/ba_net.py); the facts that follow from the `true, false,
 coin` schedule; one hand-built message sequence per fault kind and per subtle
 point of the reference's handlers; and the ABI of the GPU entry
-(hbrbc_ba_state_bytes, the hbrbc_ba_args layouts)."""
+(hbrbc_ba_state_bytes; the hbrbc_ba_args layouts are in tests/test_crate.py)."""
 import ctypes
-import importlib.util
-import os
 import random
-import re
 
 import pytest
 
@@ -18,7 +15,6 @@ from ba_net import NONE, SILENT, check_properties, run_random, run_rounds
 from hbbft_amd import binary_agreement as ba
 from hbbft_amd.binary_agreement import BinaryAgreement, CoinTable, FaultKind, Message
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BVAL, AUX, CONF, TERM, COIN = range(5)
 
 
@@ -404,23 +400,3 @@ def test_state_block_size():
             assert got == want and got % 16 == 0, (n, q, got, want)
             assert ba_state_bytes_host(n, q) == got
     assert 590 <= ba_state_bytes_host(64, 4) <= 600
-
-
-def test_ba_args_layouts_agree():
-    """HbrbcBaArgs (Rust), hbrbc_ba_args (C) and ba_sim.BaArgs (ctypes): same
-    fields in the same order, and the ctypes field types match the C ones."""
-    from hbbft_amd.ba_sim import BaArgs
-    spec = importlib.util.spec_from_file_location(
-        "gen_ffi", os.path.join(ROOT, "hbbft-hip", "gen_ffi.py"))
-    g = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(g)
-    hdr = open(os.path.join(ROOT, "include", "hbrbc.h")).read()
-    c = g.struct_fields(hdr, "hbrbc_ba_args")
-    rs = open(os.path.join(ROOT, "hbbft-hip", "src", "ffi.rs")).read()
-    body = re.search(r"pub struct HbrbcBaArgs \{(.*?)\}", rs, flags=re.S).group(1)
-    rs_fields = [(m.group(1).rstrip("_"), m.group(2)) for m in re.finditer(r"pub (\w+): ([^,]+),", body)]
-    assert [n for n, _ in c] == [n for n, _ in rs_fields] == [n.rstrip("_") for n, _ in BaArgs._fields_]
-    assert [t for _, t in c] == [t for _, t in rs_fields]
-    ctype = {"usize": ctypes.c_size_t, "u32": ctypes.c_uint32, "i32": ctypes.c_int32}
-    for (name, rt), (_, ct) in zip(c, BaArgs._fields_):
-        assert ct is (ctypes.c_void_p if rt.startswith("*") else ctype[rt]), name

@@ -56,18 +56,30 @@ def test_every_extern_matches_the_header_and_the_library():
         assert hasattr(L, name), name
 
 
-def test_sm_args_layouts_agree():
-    """HbrbcSmArgs (Rust), hbrbc_sm_args (C) and rbc_sim.SmArgs (ctypes): same
-    fields in the same order."""
-    from hbbft_amd.rbc_sim import SmArgs
-    g = _gen()
+@pytest.mark.parametrize("c_name, rs_name, module, py_name", [
+    ("hbrbc_sm_args", "HbrbcSmArgs", "rbc_sim", "SmArgs"),
+    ("hbrbc_ba_args", "HbrbcBaArgs", "ba_sim", "BaArgs"),
+    ("hbrbc_subset_args", "HbrbcSubsetArgs", "subset_sim", "SubsetArgs"),
+    ("hbrbc_hb_args", "HbrbcHbArgs", "hb_sim", "HbArgs")])
+def test_args_layouts_agree(c_name, rs_name, module, py_name):
+    """The args struct of a round entry point in Rust (src/ffi.rs), in C
+    (include/hbrbc.h) and as the ctypes Structure of its host module: same
+    fields in the same order, and the ctypes field types match the C ones."""
+    import importlib
+    py = getattr(importlib.import_module("hbbft_amd." + module), py_name)
+    assert issubclass(py, ctypes.Structure) and py.__name__ == py_name
     hdr = open(os.path.join(ROOT, "include", "hbrbc.h")).read()
-    c_fields = [n for n, _ in g.struct_fields(hdr, "hbrbc_sm_args")]
+    c = _gen().struct_fields(hdr, c_name)
     rs = open(os.path.join(CRATE, "src", "ffi.rs")).read()
-    body = re.search(r"pub struct HbrbcSmArgs \{(.*?)\}", rs, flags=re.S).group(1)
-    rs_fields = [m.group(1).rstrip("_") for m in re.finditer(r"pub (\w+):", body)]
-    py_fields = [n.rstrip("_") for n, _ in SmArgs._fields_]
-    assert c_fields == rs_fields == py_fields
+    body = re.search(r"pub struct %s \{(.*?)\}" % rs_name, rs, flags=re.S).group(1)
+    rs_fields = [(m.group(1).rstrip("_"), m.group(2))
+                 for m in re.finditer(r"pub (\w+): ([^,]+),", body)]
+    assert [n for n, _ in c] == [n for n, _ in rs_fields] == [n.rstrip("_") for n, _ in py._fields_]
+    assert [t for _, t in c] == [t for _, t in rs_fields]
+    ctype = {"usize": ctypes.c_size_t, "u32": ctypes.c_uint32, "i32": ctypes.c_int32}
+    assert len(c) == len(py._fields_) > 0
+    for (name, rt), (_, ct) in zip(c, py._fields_):
+        assert ct is (ctypes.c_void_p if rt.startswith("*") else ctype[rt]), name
 
 
 def test_facade_calls_declared_functions_only():

@@ -522,6 +522,28 @@ def test_local_rounds_run_twice_from_fresh_nodes():
     assert run_rounds([sm]) == 5 and sm.records == rec1
 
 
+def test_rounds_objects_go_with_their_last_reference():
+    """A LocalRounds holds no reference to itself (its reset / enqueue / read
+    are methods, not stored bound methods), so the ranks it holds -- device
+    buffers -- are released when the caller drops it, not at some later
+    collection of cyclic garbage."""
+    import gc
+    import weakref
+
+    from hbbft_amd.rbc_sim import LocalRounds
+    gc.collect()
+    gc.disable()
+    try:
+        sm = _FakeLocalSm()
+        lr = LocalRounds([sm], loopback=False).launch()
+        assert lr.wait() == 5
+        seen = weakref.ref(lr), weakref.ref(sm)
+        del lr, sm
+        assert seen[0]() is None and seen[1]() is None
+    finally:
+        gc.enable()
+
+
 def test_round_flags_raise_distinct_errors():
     """CPU: the per-round flags the kernels OR into emitted[1] -- bit 0 a node
     emitted more than max_out records, bit 1 a record kind (or a fake_from
@@ -530,11 +552,16 @@ def test_round_flags_raise_distinct_errors():
     the round count."""
     import torch
 
-    from hbbft_amd.rbc_sim import _check_batch
+    from hbbft_amd.rbc_sim import _protocols
+    from hbbft_amd.rounds import check_batch
 
     class _R:
         max_out = 4
         records = 0
+
+    def _check_batch(ranks, h, r0):   # the shared loop's read-back, with Broadcast's table
+        h = h.numpy()
+        return check_batch(_protocols(ranks), h, h[:, :, 0].sum(axis=0), r0)
 
     ranks = [_R()]
     ok = torch.tensor([[[5, 0], [3, 0], [0, 0]]], dtype=torch.int32)   # [ranks][rounds][2]

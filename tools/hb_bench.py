@@ -45,6 +45,7 @@ def bench_hb(n, count, encrypted, reps):
     events = []
     assert hb_sim.run_rounds(rank, events) == rounds
     torch.cuda.synchronize()
+    events = [(e0, e1) for name, e0, e1 in events if name == "phase3"]
     p3 = sum(e0.elapsed_time(e1) for e0, e1 in events)
     sub = subset_sim.SubsetRank(sscn, 0, ok, dec, **kw)
     sub_rounds, sts = sb.timed(lambda: subset_sim.run_rounds(sub), reps)

@@ -59,32 +59,17 @@ def forced_plane(n, instances, dev):
 
 
 def phase_ms(rank):
-    """One more run with a device event around every launch: (phase 1 ms,
-    phase 2 ms) summed over the rounds, from the rank's own round loop."""
+    """One more run with a device event around every launch (the round
+    loop's timing hook): (phase 1 ms, phase 2 ms) summed over the rounds."""
     import torch
+    from hbbft_amd import subset_sim
     ev = []
-    bc_round, phase2 = rank.bc.round, rank.phase2
-
-    def wrap(fn, tag):
-        def inner(*a, **kw):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn(*a, **kw)
-            e1.record()
-            ev.append((tag, e0, e1))
-        return inner
-
-    rank.bc.round, rank.phase2 = wrap(bc_round, 0), wrap(phase2, 1)
-    try:
-        from hbbft_amd import subset_sim
-        rounds = subset_sim.run_rounds(rank)
-    finally:
-        rank.bc.round, rank.phase2 = bc_round, phase2
+    rounds = subset_sim.run_rounds(rank, ev)
     torch.cuda.synchronize()
-    tot = [0.0, 0.0]
-    for tag, e0, e1 in ev:
-        tot[tag] += e0.elapsed_time(e1)
-    return rounds, tot
+    tot = {"phase1": 0.0, "phase2": 0.0}
+    for name, e0, e1 in ev:
+        tot[name] += e0.elapsed_time(e1)
+    return rounds, [tot["phase1"], tot["phase2"]]
 
 
 def bench_subset(n, count, reps):
